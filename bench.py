@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark (BASELINE.json): Mpixels/s of the DCT-II + DCT-III roundtrip on
 3840x2160x3 f32 frames, device-resident, as a fraction of the MI355X HBM roofline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ...`, one rank per GPU)
 
 A "step" = one roundtrip (2-D REDFT10 in place, then 2-D REDFT01 in place with the 1/(4wh) gain
@@ -31,6 +31,7 @@ HBM_PEAK = 8.0e12                 # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s 
 SEED = 0xD5F0002
 DRIFT_PER_ROUNDTRIP = 2e-6        # growth of |frame - input| per in-place roundtrip allowed in a run (measured: 8.4e-7; ONE roundtrip is pinned at
 DRIFT_BOUND = 1e-3                # <= 5e-6 by tests/test_gpu_parity.py): the sanity bound is max(DRIFT_BOUND, n * DRIFT_PER_ROUNDTRIP) -- set in main()
+DUMP_SAMPLES = 8 << 20            # --dump-outputs: float32 elements written at most (32 MB, under the 64 MB cap)
 
 
 def synth_frames(torch, nframes, device):
@@ -291,6 +292,24 @@ def fftw_abi_end_to_end(reps=8):
             "executes_timed": reps}
 
 
+def dump_frames(torch, frames, out_dir):
+    """--dump-outputs: what the timed path hands its caller -- the frames after the last in-place roundtrip -- as DIR/frames.npy (float32).  All
+    frames together are far above 64 MB (4 x 99.5 MB by default), so a fixed sample of them is written: DUMP_SAMPLES flat indices into
+    (frames, H, W, C) drawn from a generator seeded with SEED, sorted.  Same arguments, same indices and same inputs: two builds compare element for element."""
+    import numpy as np
+    n = frames.numel()
+    if n <= DUMP_SAMPLES:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(SEED).integers(0, n, size=DUMP_SAMPLES, dtype=np.int64))
+    sample = frames.reshape(-1)[torch.from_numpy(idx).to(frames.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "frames.npy")
+    np.save(path, sample)
+    return {"dir": out_dir, "arrays": {"frames": {"dtype": "float32", "elements": int(sample.size), "of": n, "shape_sampled": list(frames.shape),
+            "sample": "all elements" if n <= DUMP_SAMPLES else f"{DUMP_SAMPLES} sorted flat indices from numpy default_rng({SEED:#x}).integers(0, {n})"}}}
+
+
 def self_launch(ngpus):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py ...`
     as a child (one rank per GPU, RCCL rendezvous on 127.0.0.1) and return its exit code."""
@@ -324,7 +343,11 @@ def main():
     ap.add_argument("--no-motion", action="store_true", help="skip the motion_c5 object (BASELINE configs[4]: per-frame blocks and the RCCL slab volume)")
     ap.add_argument("--extras-timeout", type=float, default=300.0, help="N > 1 only: seconds the motion_c5 / scan_c4 objects may take after the headline before the line is printed without them")
     ap.add_argument("--no-scan", action="store_true", help="skip the scan_c4 object (BASELINE configs[3]: channel-sharded progressive reconstruct of an 8K frame)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write a fixed sample of the frames the last step returned to DIR/frames.npy "
+                    "(float32, rank 0), so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # called directly as `python bench.py --gpus N`: start the N ranks ourselves, as a CHILD process of a parent
@@ -448,6 +471,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the frames as the last timed step left them, before any later leg transforms them again (every rank holds the same frames)
+    dumped = dump_frames(torch, frames, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # the same batch on ONE stream (each frame's four launches alone on the chip), untimed-warm, then K steps between synchronisations:
     # what the two-stream schedule buys is value / single_stream_value
     single_stream_value = None
@@ -578,6 +603,8 @@ def main():
             "closing_bracket_ms": {"synchronize": closing[0], "barrier": closing[1], "synchronize_after": closing[2]},
             "roofline": roof,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if motion is not None:
             line["motion_c5"] = motion
         if scan is not None:

@@ -118,15 +118,11 @@ class _OrderList(C.Structure):
     _fields_ = [("limit", C.c_size_t), ("max_interval", C.c_size_t), ("total", C.c_size_t), ("offset", C.POINTER(C.c_size_t)), ("yx", C.POINTER(C.c_size_t * 2))]
 
 
-class _Precomputed(C.Structure):          # scan/scan_precomputed.h:12-16
-    _fields_ = [("limit", C.c_size_t), ("intervals", C.POINTER(C.c_size_t)), ("scans", C.POINTER(C.POINTER(C.c_size_t * 2)))]
-
-
 @pytest.mark.parametrize("method,w,h", [("diagonal", 8, 8), ("box", 16, 9), ("ibox", 9, 16), ("mirror", 7, 5), ("zigzag", 6, 4), ("radial", 10, 6)])
 @pytest.mark.parametrize("fmt", ["coordinate", "index"])
 def test_file_method_reader_roundtrips_and_matches_the_reference_deserialiser(so, method, w, h, fmt):
     """`file` (scan_methods.c:393-410): host/scan_orders.c scan_order_read_file on both plaintext serialisations, against the
-    generator that wrote the file and against the REFERENCE's own scan_precomputed_unserialize (oracle/_ref)."""
+    generator that wrote the file and against what the REFERENCE's own scan_precomputed_unserialize read from it (tests/golden/ref_lib.npz)."""
     libc = C.CDLL(None)
     libc.fopen.restype = C.c_void_p
     libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
@@ -163,17 +159,13 @@ def test_file_method_reader_roundtrips_and_matches_the_reference_deserialiser(so
             for x in range(w):
                 want[owner[(y, x)]].append((y, x))
         assert got == want
-    # the reference's deserialiser on the same file
-    r = ol.ref()
-    if r is not None:
-        r.scan_precomputed_unserialize.restype = C.POINTER(_Precomputed)
-        r.scan_precomputed_unserialize.argtypes = [C.c_void_p]
-        f = libc.fopen(path.encode(), b"r")
-        p = r.scan_precomputed_unserialize(f)
-        libc.fclose(f)
-        assert p and p.contents.limit == lst.limit
-        refl = [[(p.contents.scans[i][j][0], p.contents.scans[i][j][1]) for j in range(p.contents.intervals[i])] for i in range(p.contents.limit)]
-        assert refl == got
+    # the reference's deserialiser on the same file (tests/golden/ref_lib.npz: tests/golden/make_ref_lib.py ran it on this serialisation)
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "ref_lib.npz"))
+    iv, yx = fx[f"scanfile_{method}_{w}x{h}_{fmt}_intervals"], fx[f"scanfile_{method}_{w}x{h}_{fmt}_yx"]
+    assert len(iv) == lst.limit
+    ends = np.cumsum(iv)
+    refl = [[(int(y), int(x)) for (y, x) in yx[e - n:e]] for n, e in zip(iv, ends)]
+    assert refl == got
     so.scan_order_list_free(C.byref(lst))
     # out-of-range coordinates are rejected like init_file does
     f = libc.fopen(path.encode(), b"r")
