@@ -20,7 +20,7 @@ SYMBOLS = [
     "dspfft_execute", "dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
     "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
     "dspfft_last_error", "dspfft_version", "dspfft_set_thread_plan_effort", "dspfft_get_thread_plan_effort", "dspfft_fftw_sparse_uploads",
-    "dspfft_scan_zigzag", "dspfft_scan_zigzag_frame_ids", "dspfft_execute_masked_accumulate", "dspfft_scan_scatter", "dspfft_accumulate", "dspfft_broadcast_dc",
+    "dspfft_scan_zigzag", "dspfft_scan_zigzag_frame_ids", "dspfft_execute_masked_accumulate", "dspfft_execute_masked_accumulate_range", "dspfft_execute_masked_accumulate_range_f64", "dspfft_scan_scatter", "dspfft_accumulate", "dspfft_broadcast_dc",
     "dspfft_scan_limit", "dspfft_scan_max_interval", "dspfft_scan_coord_slots", "dspfft_scan_owner_index", "dspfft_scan_frame_ids", "dspfft_scan_coords", "dspfft_scan_stamp",
     "dspfft_scan_index_to_frame_ids", "dspfft_scan_magnitude_work_bytes", "dspfft_scan_magnitude_index",
     "dspfft_u8_to_f32", "dspfft_f32_to_u8",
@@ -107,6 +107,8 @@ def bind(lib):
     lib.dspfft_scan_zigzag.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]
     lib.dspfft_scan_zigzag_frame_ids.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, vp]
     lib.dspfft_execute_masked_accumulate.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_int, vp]
+    lib.dspfft_execute_masked_accumulate_range.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp]
+    lib.dspfft_execute_masked_accumulate_range_f64.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp]
     lib.dspfft_scan_limit.restype = C.c_uint64
     lib.dspfft_scan_limit.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
     lib.dspfft_scan_max_interval.restype = C.c_uint64

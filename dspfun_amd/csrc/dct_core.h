@@ -93,9 +93,10 @@ struct PassGeom {
 	                             // x pass writes the blocks of ALL destination ranks in one launch (dist.py SlabDCT3D)
 	const uint32_t *pos;  // pos[k] = LDS slot holding FFT output k after the DIF stages
 	// fused scan step (scan/scan.c:429-459): the FIRST pass zeroes every input element whose owner
-	// id differs (mask[offset / mask_div] != mask_id); the LAST pass adds into `out` instead of storing
+	// id lies outside [mask_id, mask_id + mask_span) (mask_pick); the LAST pass adds into `out` instead of storing
 	const uint32_t *mask;
 	uint32_t mask_id;
+	uint32_t mask_span;   // 1: the one frame id mask_id
 	FastDiv mask_div;     // elements per owner id (32-bit offsets: masked runs are limited to 2^32 / d elements)
 	int mask_mode;        // column tiles (dct_spec.h, masked_two_step): 0 = owner ids from `mask`, item by item; 1 / 2 = from `eids`, one / two bytes per id
 	const void *eids;     // dspfft_plan_scan_prepare: the owner id of every element, in column-tile order (eid_index); needs zpage
@@ -139,18 +140,22 @@ template <class R> struct vec_of;
 template <> struct vec_of<float> { typedef float4 v16; typedef float2 v2; };
 template <> struct vec_of<double> { typedef double2 v16; typedef double2 v2; };
 
+// owner id `id` belongs to the masked step's range [lo, lo + span): one subtract and one compare (span 1 is the old equality).
+// The DC pixel's 0xFFFFFFFF is never in a range whose end lo + span fits in 32 bits (dspfft_execute_masked_accumulate_range)
+DSP_HD bool mask_pick(uint32_t id, uint32_t lo, uint32_t span) { return id - lo < span; }
+
 template <class R>
 DSP_HD R masked(const PassArgsT<R> &a, long long off, R v)
 {
 	if (!a.mask) return v;
-	return a.mask[a.mask_div.div((uint32_t)off)] != a.mask_id ? R(0) : v;
+	return !mask_pick(a.mask[a.mask_div.div((uint32_t)off)], a.mask_id, a.mask_span) ? R(0) : v;
 }
 // a.in[off] under the mask, without fetching elements that are masked out.  MASKED is chosen once per phase (a.mask
 // is uniform): a test around every load would make each load wait for its data before the next one is issued
 template <bool MASKED, class R>
 DSP_HD R load_masked(const PassArgsT<R> &a, long long off)
 {
-	if constexpr (MASKED) { if (a.mask[a.mask_div.div((uint32_t)off)] != a.mask_id) return R(0); }
+	if constexpr (MASKED) { if (!mask_pick(a.mask[a.mask_div.div((uint32_t)off)], a.mask_id, a.mask_span)) return R(0); }
 	return a.in[off];
 }
 
@@ -585,7 +590,7 @@ struct TinyGeom {
 	int packed;                               // lines lie back to back (dimension 0 has stride N): chunked through LDS
 	FastDiv chunk_div;                        // chunks per run of dimension 0
 	const uint32_t *mask;
-	uint32_t mask_id;
+	uint32_t mask_id, mask_span;              // see PassGeom
 	FastDiv mask_div;
 	int accumulate;
 };
@@ -688,7 +693,7 @@ DSP_HD void tiny_line(const TinyArgsT<R> &a, long long line)
 #pragma unroll
 	for (int j = 0; j < N; j++) {
 		const long long off = bin + (long long)j * a.es_in;
-		const bool drop = a.mask && a.mask[a.mask_div.div((uint32_t)off)] != a.mask_id;
+		const bool drop = a.mask && !mask_pick(a.mask[a.mask_div.div((uint32_t)off)], a.mask_id, a.mask_span);
 		x[j] = drop ? R(0) : a.in[off];
 	}
 	tiny_dct<N, KIND>(a, x, y);
@@ -710,7 +715,7 @@ DSP_HD void tiny_row_load(const TinyArgsT<R> &a, R *lds, long long bin, int cnt,
 {
 	for (int e = tid; e < cnt * N; e += nthr) {
 		const long long off = bin + e;
-		const bool drop = a.mask && a.mask[a.mask_div.div((uint32_t)off)] != a.mask_id;
+		const bool drop = a.mask && !mask_pick(a.mask[a.mask_div.div((uint32_t)off)], a.mask_id, a.mask_span);
 		lds[(e / N) * tiny_pitch<N>() + e % N] = drop ? R(0) : a.in[off];
 	}
 }
@@ -754,7 +759,7 @@ struct DenseGeom {
 	int nb0, nb1, nb2;                       // three batch levels
 	long long sb0_in, sb1_in, sb2_in, sb0_out, sb1_out, sb2_out;
 	const uint32_t *mask;
-	uint32_t mask_id;
+	uint32_t mask_id, mask_span;              // see PassGeom
 	FastDiv mask_div;
 	int accumulate;
 };
@@ -782,7 +787,7 @@ DSP_HD void dense_load(const DenseArgsT<R> &a, R *x, long long bin, int tid, int
 {
 	for (int j = tid; j < a.N; j += nthr) {
 		const long long off = bin + (long long)j * a.es_in;
-		const R v = (a.mask && a.mask[a.mask_div.div((uint32_t)off)] != a.mask_id) ? R(0) : a.in[off];
+		const R v = (a.mask && !mask_pick(a.mask[a.mask_div.div((uint32_t)off)], a.mask_id, a.mask_span)) ? R(0) : a.in[off];
 		x[j] = v * (j == 0 ? a.in_scale0 : R(1));
 	}
 }

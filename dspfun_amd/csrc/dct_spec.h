@@ -128,11 +128,11 @@ template <int C, bool MASKED, class Re> DSP_HD Pix<C, Re> load_pix_m(const PassA
 		// (a frame keeps 1/32 of them at BASELINE config 4, so most of the first pass's reads disappear)
 		uint32_t id[C];
 		bool any = false;
-		static_for<0, C>([&](auto c) { id[c] = a.mask[a.mask_div.div((uint32_t)(off + c))]; any = any || id[c] == a.mask_id; });
+		static_for<0, C>([&](auto c) { id[c] = a.mask[a.mask_div.div((uint32_t)(off + c))]; any = any || mask_pick(id[c], a.mask_id, a.mask_span); });
 		Pix<C, Re> v;
 		if (!any) { static_for<0, C>([&](auto c) { v.v[c] = (Re)0; }); return v; }
 		v = load_pix<C, Re>(a.in + off);
-		static_for<0, C>([&](auto c) { if (id[c] != a.mask_id) v.v[c] = (Re)0; });
+		static_for<0, C>([&](auto c) { if (!mask_pick(id[c], a.mask_id, a.mask_span)) v.v[c] = (Re)0; });
 		return v;
 	}
 	return load_pix<C, Re>(a.in + off);
@@ -171,13 +171,13 @@ template <bool MASKED, class Re> DSP_HD typename sig_of<Re>::type loadv_m(const 
 			static_for<0, 2 * NCS>([&](auto c) { id[c] = a.mask[own[c]]; });
 		}
 		bool any = false;
-		static_for<0, 2 * NCS>([&](auto c) { any = any || id[c] == a.mask_id; });
+		static_for<0, 2 * NCS>([&](auto c) { any = any || mask_pick(id[c], a.mask_id, a.mask_span); });
 		V v;
 		static_for<0, NCS>([&](auto i) { v.s[i].x = v.s[i].y = (Re)0; });
 		if (!any) return v;
 		hit = true;                  // this thread selected at least one coefficient (sparse scan frames: see PassGeom::zflags)
 		v = *reinterpret_cast<const V *>(a.in + off);
-		static_for<0, NCS>([&](auto i) { if (id[2 * i] != a.mask_id) v.s[i].x = (Re)0; if (id[2 * i + 1] != a.mask_id) v.s[i].y = (Re)0; });
+		static_for<0, NCS>([&](auto i) { if (!mask_pick(id[2 * i], a.mask_id, a.mask_span)) v.s[i].x = (Re)0; if (!mask_pick(id[2 * i + 1], a.mask_id, a.mask_span)) v.s[i].y = (Re)0; });
 		return v;
 	}
 	return *reinterpret_cast<const V *>(a.in + off);
@@ -188,7 +188,8 @@ template <bool MASKED, class Re> DSP_HD typename sig_of<Re>::type loadv_m(const 
 // 128-byte line per tile ROW for 22 bytes of it: 6.8 M L2 requests per 8K frame, every one a miss in the vector L1 -- the 8K column pass
 // spent 155 of its 200 us on them, whatever the order of the loads and whichever XCD the neighbours ran on (profiles/r04_scan_mask.txt).
 // Two steps: all ids of a thread's items, then all coefficients (an item nobody selected is not loaded).
-// EB = bytes per id; ids that do not fit (and the DC pixel's "no frame") are stored as all ones and match no frame the table is used for.
+// EB = bytes per id; ids that do not fit (and the DC pixel's "no frame") are stored as all ones and match no range the table is used for
+// (the engine clamps both ends of the range to all ones, so a range reaching past the table's ids stays one subtract and one compare).
 template <int EB, class Re> struct MaskIds { uint32_t v[EB == 1 ? 1 : 2 * sig_of<Re>::NCS * EB / 4]; };
 template <int EB, class Re> DSP_HD void mask_fetch_ids(const PassArgsT<Re> &a, long long eoff, MaskIds<EB, Re> &m)
 {
@@ -200,12 +201,12 @@ template <int EB, class Re> DSP_HD typename sig_of<Re>::type mask_select_load(co
 {
 	typedef typename sig_of<Re>::type V;
 	constexpr int NCS = sig_of<Re>::NCS, NE = 2 * NCS;
-	const uint32_t want = a.mask_id, ones = EB == 1 ? 0xffu : 0xffffu;
+	const uint32_t ones = EB == 1 ? 0xffu : 0xffffu;
 	bool sel[NE];
 	bool any = false;
 	static_for<0, NE>([&](auto c) {
 		constexpr int bit = c * 8 * EB;
-		sel[c] = ((m.v[bit / 32] >> (bit % 32)) & ones) == want;
+		sel[c] = mask_pick((m.v[bit / 32] >> (bit % 32)) & ones, a.mask_id, a.mask_span);
 		any = any || sel[c];
 	});
 	hit = hit || any;

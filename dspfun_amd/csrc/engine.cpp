@@ -720,7 +720,7 @@ int build_pass(dspfft_plan_s *pl, int a, bool first, Pass &P)
 	}
 }
 
-struct Fuse { const void *eids = nullptr; int eid_bytes = 0; const uint32_t *mask = nullptr; uint32_t id = 0; int div = 1; bool accumulate = false; uint8_t *zflags = nullptr; int zshift = 0, zhalf = 0; const void *zpage = nullptr; const uint32_t *zranges = nullptr; };
+struct Fuse { const void *eids = nullptr; int eid_bytes = 0; const uint32_t *mask = nullptr; uint32_t id = 0, span = 1; int div = 1; bool accumulate = false; uint8_t *zflags = nullptr; int zshift = 0, zhalf = 0; const void *zpage = nullptr; const uint32_t *zranges = nullptr; };
 FastDiv make_div(uint32_t d);
 
 template <class R>
@@ -729,11 +729,16 @@ void fill_args(PassArgsT<R> &a, const PassGeom &g, const dspfft_plan_s *pl, cons
 	static_cast<PassGeom &>(a) = g;
 	a.in = in; a.out = out; a.T = (const cx<R> *)P.tab.T; a.W = (const cx<R> *)P.tab.W; a.H = (const cx<R> *)P.tab.H;
 	a.scale = (R)scale; a.in_scale0 = (R)pl->in0[P.axis]; a.out_scale0 = (R)pl->out0[P.axis];
-	a.mask = fz.mask; a.mask_id = fz.id; a.mask_div = make_div((uint32_t)fz.div); a.accumulate = fz.accumulate;
+	a.mask = fz.mask; a.mask_id = fz.id; a.mask_span = fz.span; a.mask_div = make_div((uint32_t)fz.div); a.accumulate = fz.accumulate;
 	a.zflags = fz.zflags; a.zshift = fz.zshift; a.zhalf = fz.zhalf; a.zpage = fz.zpage; a.zranges = fz.zranges;
-	// masked column tiles take their owner ids from the plan's element-order table where one was prepared for this id array and the frame id fits it
+	// masked column tiles take their owner ids from the plan's element-order table where one was prepared for this id array and the range
+	// starts below its saturated value; the range's end is clamped to that value (every id of such a table lies below it but DC's)
 	a.mask_mode = 0; a.eids = nullptr;
-	if (fz.mask && fz.zpage && fz.eids && fz.eid_bytes && fz.id < (fz.eid_bytes == 1 ? 0xffu : 0xffffu)) { a.mask_mode = fz.eid_bytes; a.eids = fz.eids; }
+	const uint32_t ones = fz.eid_bytes == 1 ? 0xffu : 0xffffu;
+	if (fz.mask && fz.zpage && fz.eids && fz.eid_bytes && fz.id < ones) {
+		a.mask_mode = fz.eid_bytes; a.eids = fz.eids;
+		a.mask_span = (uint32_t)std::min<uint64_t>((uint64_t)fz.id + fz.span, ones) - fz.id;
+	}
 	a.alt_out = (pl->alt_axis == P.axis && pl->alt_axis >= 0) ? 1 : 0;
 	static const int lean_off = []() { const char *e = getenv("DSPFFT_LEAN01"); return e && *e == '0' ? 1 : 0; }();
 	a.lean_off = lean_off;
@@ -777,14 +782,14 @@ int run_pass(const dspfft_plan_s *pl, const Pass &P, const R *in, R *out, bool l
 			static_cast<TinyGeom &>(a) = P.tg;
 			a.in = in + oin; a.out = out + oout;
 			a.scale = (R)scale; a.in_scale0 = (R)pl->in0[P.axis]; a.out_scale0 = (R)pl->out0[P.axis];
-			a.mask = fz.mask; a.mask_id = fz.id; a.mask_div = make_div((uint32_t)fz.div); a.accumulate = fz.accumulate;
+			a.mask = fz.mask; a.mask_id = fz.id; a.mask_span = fz.span; a.mask_div = make_div((uint32_t)fz.div); a.accumulate = fz.accumulate;
 			rc = be_launch_tiny(a, stream);
 		} else if (P.type == Pass::DENSE) {
 			DenseArgsT<R> a;
 			static_cast<DenseGeom &>(a) = P.da;
 			a.in = in + oin; a.out = out + oout; a.cosTab = (const R *)P.tab.cosTab; a.stage = (R *)P.tab.stage;
 			a.scale = (R)scale; a.in_scale0 = (R)pl->in0[P.axis]; a.out_scale0 = (R)pl->out0[P.axis];
-			a.mask = fz.mask; a.mask_id = fz.id; a.mask_div = make_div((uint32_t)fz.div); a.accumulate = fz.accumulate;
+			a.mask = fz.mask; a.mask_id = fz.id; a.mask_span = fz.span; a.mask_div = make_div((uint32_t)fz.div); a.accumulate = fz.accumulate;
 			rc = be_launch_dense(a, P.g, stream);
 		} else {
 			bool use_spec = false;
@@ -1182,7 +1187,7 @@ int execute_t(dspfft_plan pl, const R *d_in, R *d_out, void *stream)
 	return 0;
 }
 template <class R>
-int execute_masked_accumulate_t(dspfft_plan pl, const R *d_in, R *d_work, R *d_acc, const uint32_t *d_ids, uint32_t id, int elems_per_id, void *stream);
+int execute_masked_accumulate_t(dspfft_plan pl, const R *d_in, R *d_work, R *d_acc, const uint32_t *d_ids, uint32_t lo, uint32_t span, int elems_per_id, void *stream);
 }  // namespace
 
 extern "C" int dspfft_execute(dspfft_plan pl, const float *d_in, float *d_out, void *stream) { return execute_t<float>(pl, d_in, d_out, stream); }
@@ -1190,12 +1195,25 @@ extern "C" int dspfft_execute_f64(dspfft_plan pl, const double *d_in, double *d_
 extern "C" int dspfft_execute_masked_accumulate(dspfft_plan pl, const float *d_in, float *d_work, float *d_acc,
                                                 const uint32_t *d_ids, uint32_t id, int elems_per_id, void *stream)
 {
-	return execute_masked_accumulate_t<float>(pl, d_in, d_work, d_acc, d_ids, id, elems_per_id, stream);
+	return execute_masked_accumulate_t<float>(pl, d_in, d_work, d_acc, d_ids, id, 1, elems_per_id, stream);
 }
 extern "C" int dspfft_execute_masked_accumulate_f64(dspfft_plan pl, const double *d_in, double *d_work, double *d_acc,
                                                     const uint32_t *d_ids, uint32_t id, int elems_per_id, void *stream)
 {
-	return execute_masked_accumulate_t<double>(pl, d_in, d_work, d_acc, d_ids, id, elems_per_id, stream);
+	return execute_masked_accumulate_t<double>(pl, d_in, d_work, d_acc, d_ids, id, 1, elems_per_id, stream);
+}
+// [lo, hi) as (lo, span): hi <= 0xFFFFFFFF keeps the DC pixel's 0xFFFFFFFF out of every range (mask_pick); hi <= lo selects nothing
+extern "C" int dspfft_execute_masked_accumulate_range(dspfft_plan pl, const float *d_in, float *d_work, float *d_acc,
+                                                      const uint32_t *d_ids, uint32_t lo, uint32_t hi, int elems_per_id, void *stream)
+{
+	if (!d_ids) return fail(-1, "dspfft_execute_masked_accumulate_range needs an owner-id array");
+	return execute_masked_accumulate_t<float>(pl, d_in, d_work, d_acc, d_ids, lo, hi > lo ? hi - lo : 0, elems_per_id, stream);
+}
+extern "C" int dspfft_execute_masked_accumulate_range_f64(dspfft_plan pl, const double *d_in, double *d_work, double *d_acc,
+                                                          const uint32_t *d_ids, uint32_t lo, uint32_t hi, int elems_per_id, void *stream)
+{
+	if (!d_ids) return fail(-1, "dspfft_execute_masked_accumulate_range_f64 needs an owner-id array");
+	return execute_masked_accumulate_t<double>(pl, d_in, d_work, d_acc, d_ids, lo, hi > lo ? hi - lo : 0, elems_per_id, stream);
 }
 
 namespace {
@@ -1274,7 +1292,7 @@ extern "C" int dspfft_plan_scan_prepare(dspfft_plan pl, const uint32_t *d_ids, i
 
 namespace {
 template <class R>
-int execute_masked_accumulate_t(dspfft_plan pl, const R *d_in, R *d_work, R *d_acc, const uint32_t *d_ids, uint32_t id, int elems_per_id, void *stream)
+int execute_masked_accumulate_t(dspfft_plan pl, const R *d_in, R *d_work, R *d_acc, const uint32_t *d_ids, uint32_t lo, uint32_t span, int elems_per_id, void *stream)
 {
 	if (!pl || !d_in || !d_work || !d_acc) return fail(-1, "null plan or buffer");
 	if (pl->f64 != std::is_same<R, double>::value) return fail(-1, "plan and buffers differ in sample type");
@@ -1308,7 +1326,9 @@ int execute_masked_accumulate_t(dspfft_plan pl, const R *d_in, R *d_work, R *d_a
 				zflags = (uint8_t *)pl->zflags; zhalf = split_ok ? gc.ntiles : 0;
 				while ((1 << zshift) < gc.K) zshift++;
 				if (pl->zranges && pl->zr_ids == (const void *)d_ids && pl->zr_div == elems_per_id && pl->zr_split == split_ok) {
-					zranges = (const uint32_t *)pl->zranges;
+					// the (min, max) tile skip compares one frame id (the column launchers' test, which the CPU emulation of the kernels repeats);
+					// a range of several ids reads the tiles' ids and still skips the tiles that selected nothing
+					zranges = span == 1 ? (const uint32_t *)pl->zranges : nullptr;
 					if (pl->eid_bytes) { eids = pl->eids; eid_bytes = pl->eid_bytes; }
 				}
 			}
@@ -1319,7 +1339,7 @@ int execute_masked_accumulate_t(dspfft_plan pl, const R *d_in, R *d_work, R *d_a
 		const Pass &P = passes[np == 2 ? order[i] : i];
 		const bool firstp = i == 0, lastp = i + 1 == np;
 		Fuse fz;
-		if (firstp && d_ids) { fz.mask = d_ids; fz.id = id; fz.div = elems_per_id; }
+		if (firstp && d_ids) { fz.mask = d_ids; fz.id = lo; fz.span = span; fz.div = elems_per_id; }
 		fz.accumulate = lastp;
 		fz.zflags = zflags; fz.zshift = zshift; fz.zhalf = zhalf; fz.zpage = pl->zpage; fz.zranges = zranges;
 		if (firstp && std::is_same<R, float>::value) { fz.eids = eids; fz.eid_bytes = eid_bytes; }

@@ -323,3 +323,118 @@ class ChannelShardedScan:
         for z in range(self.c):
             out[:, :, z] = recv[z % self.G][z // self.G]
         return out
+
+
+#: scan method names in the numbering of include/dspfft.h (DSPFFT_SCAN_*)
+SCAN_METHODS = ["horizontal", "vertical", "zigzag", "row", "column", "diagonal", "mirror", "box", "ibox", "radial", "iradial"]
+_NONE = 0xFFFFFFFF
+
+
+class FrameShardedScan:
+    """scan's progressive reconstruction (scan/scan.c:346-459) with the OUTPUT FRAMES spread over the ranks, the four frame-loop options
+    included: offset (-O, with the fill of :389-417 unless fill=False, i.e. --skip), invert (-I) and nframes (-n).
+
+    The step is linear -- sum_k = sum_{k-1} + D3(c * mask_k) -- so a rank that owns frames [f0, f1) starts from the DC broadcast + the fill
+    + ONE range-masked inverse (dspfft_execute_masked_accumulate_range) over every scan index the loop adds before f0, and then runs its own
+    frames with the fused step: no collective anywhere.  Every rank holds the whole interleaved image (its own forward, 1/(4wh) fused).
+    The loop frames [offset, offset + nframes) are dealt in contiguous ranges whose sizes differ by at most one (shard_range: equal
+    blocks would leave the last ranks empty, e.g. 2, 2, 1, 0 frames for 5 on 4 ranks); with G ranks a rank runs at most
+    ceil(nframes / G) + 1 step-equivalents, so the ceiling of the speed-up is nframes / (ceil(nframes / G) + 1): 3.56x for 32 frames
+    on 4 GPUs, 6.4x on 8, against 3.0x for ChannelShardedScan, which leaves ranks beyond the colour planes idle.  G = 1 is the
+    single-GPU device scan with those options.
+
+    Frames come out on their owner only.  A caller who needs them in order collects frame i from owner(i): e.g. every rank runs its
+    next_frame() in lock step and then, for the frame of each rank, dist.broadcast(sum, src=owner(i)) into a buffer of its own.
+
+    Reference arithmetic kept as it is (scan.c:347-348,385-386,389-424): nframes = 0 or > limit/step becomes ceil(limit/step); offset >= limit
+    becomes limit - 1; the fill adds scan indices [0, offset) (inverted: [limit - offset, limit)) while the loop starts at FRAME offset, i.e.
+    scan index offset * step, so with step > 1 indices [offset, offset * step) are never added; frames past limit add nothing.
+    Methods: every one dspfft_scan_frame_ids takes (box has no owner index: host/scan_dev stamps its frames instead)."""
+
+    def __init__(self, image_hwc, step, method="zigzag", offset=0, fill=True, invert=False, nframes=0, group=None, lib=None):
+        from . import _lib
+        if method == "box":
+            raise ValueError("FrameShardedScan: box has no owner index (a pixel can belong to several scan indices); host/scan_dev runs it by stamps")
+        if method not in SCAN_METHODS:
+            raise ValueError(f"FrameShardedScan: unknown scan method {method!r}")
+        self.lib = lib or _lib.load()
+        self.group = group
+        self.G = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self.h, self.w, self.c = image_hwc.shape
+        self.step = int(step)
+        if self.step < 1:
+            raise ValueError("step must be >= 1")
+        self.method = SCAN_METHODS.index(method)
+        self.invert, self.fill = bool(invert), bool(fill)
+        self.limit = int(self.lib.dspfft_scan_limit(self.method, self.w, self.h))
+        nframes = int(nframes)
+        if not nframes or nframes > self.limit // self.step:                    # scan.c:347-348
+            nframes = (self.limit + self.step - 1) // self.step
+        self.nframes = nframes
+        self.offset = min(int(offset), self.limit - 1)                          # scan.c:385-386
+        lo, hi = shard_range(self.nframes, self.rank, self.G)
+        self.f0, self.f1 = self.offset + lo, self.offset + hi
+        self._st = SlabDCT3D._stream(image_hwc) or None
+        self.coeffs = image_hwc.contiguous().clone()
+        fwd = Plan.image(self.h, self.w, self.c, REDFT10, lib=lib).set_scale(1.0 / (4.0 * self.w * self.h))
+        fwd.execute(self.coeffs.data_ptr(), stream=self._st or 0)
+        self.inv = Plan.image(self.h, self.w, self.c, REDFT01, lib=lib)
+        dev = image_hwc.device
+        # the owner index with DC unmarked (scan.c:406,445 clear it before every inverse): the fill, the prefix and every inverted frame
+        self.index = torch.empty(self.w * self.h, dtype=torch.int32, device=dev)
+        self._check(self.lib.dspfft_scan_owner_index(self.index.data_ptr(), self.method, self.w, self.h, self._st))
+        self.index[0] = -1
+        # forward frames: the frame ids of the single-GPU loop, prepared (tile ranges, element-id table) as ChannelShardedScan does
+        self.ids = None
+        if not self.invert:
+            self.ids = torch.empty(self.w * self.h, dtype=torch.int32, device=dev)
+            self._check(self.lib.dspfft_scan_frame_ids(self.ids.data_ptr(), self.method, self.w, self.h, self.step, self._st))
+        self.inv.scan_prepare((self.index if self.invert else self.ids).data_ptr(), self.c, stream=self._st or 0)
+        self.work = torch.empty_like(self.coeffs)
+        self.sum = torch.empty_like(self.coeffs)
+        self.start()
+
+    def _check(self, rc):
+        if rc:
+            raise RuntimeError(self.lib.dspfft_last_error().decode())
+
+    def _mirror(self, lo, hi):
+        """scan indices [lo, hi) of the loop's order as owner indices: themselves, or limit - 1 - s when inverted (scan.c:391,424)"""
+        lo, hi = min(lo, self.limit), min(hi, self.limit)
+        return (self.limit - hi, self.limit - lo) if self.invert else (lo, hi)
+
+    def _add_range(self, lo, hi):
+        if hi > lo:
+            self.inv.execute_masked_accumulate_range(self.coeffs.data_ptr(), self.work.data_ptr(), self.sum.data_ptr(), self.index.data_ptr(),
+                                                     lo, hi, self.c, stream=self._st or 0)
+
+    def start(self):
+        """the rank's starting sum: DC everywhere (scan.c:377-383), the fill of scan indices [0, offset) (:389-417), and one range inverse
+        over the loop's scan indices before f0 -- not contiguous with the fill when step > 1, hence two calls.  Rewinds to frame f0."""
+        self._check(self.lib.dspfft_broadcast_dc(self.sum.data_ptr(), self.coeffs.data_ptr(), self.w * self.h, self.c, self._st))
+        if self.fill:
+            self._add_range(*self._mirror(0, self.offset))
+        self._add_range(*self._mirror(self.offset * self.step, self.f0 * self.step))
+        self.frame = self.f0
+
+    def owner(self, i):
+        """rank that emits loop frame i (None outside [offset, offset + nframes))"""
+        if not self.offset <= i < self.offset + self.nframes:
+            return None
+        base, rem = divmod(self.nframes, self.G)          # shard_range: the first rem ranks hold base + 1 frames
+        k = i - self.offset
+        return k // (base + 1) if k < rem * (base + 1) else rem + (k - rem * (base + 1)) // base
+
+    def next_frame(self):
+        """adds frame self.frame (scan.c:421-459) and returns its number, or None when the rank's frames are done"""
+        i = self.frame
+        if i >= self.f1:
+            return None
+        if self.invert:
+            self._add_range(*self._mirror(i * self.step, (i + 1) * self.step))
+        else:
+            self.inv.execute_masked_accumulate(self.coeffs.data_ptr(), self.work.data_ptr(), self.sum.data_ptr(), self.ids.data_ptr(), i, self.c,
+                                               stream=self._st or 0)
+        self.frame = i + 1
+        return i

@@ -146,6 +146,13 @@ class Plan:
         self._check(run(
             self._h, C.c_void_p(d_in), C.c_void_p(d_work), C.c_void_p(d_acc), C.c_void_p(d_ids or None), frame_id, elems_per_id, C.c_void_p(stream)))
 
+    def execute_masked_accumulate_range(self, d_in, d_work, d_acc, d_ids, lo, hi, elems_per_id=1, stream=0):
+        """d_acc += plan(d_in where lo <= ids < hi) (dspfft_execute_masked_accumulate_range): the id 0xFFFFFFFF (DC, unowned) is never
+        selected; hi <= lo adds nothing"""
+        run = self._lib.dspfft_execute_masked_accumulate_range_f64 if self.f64 else self._lib.dspfft_execute_masked_accumulate_range
+        self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_work), C.c_void_p(d_acc), C.c_void_p(d_ids), int(lo), int(hi), elems_per_id,
+                        C.c_void_p(stream)))
+
     def execute_sum2(self, other, d_in, d_in_other, d_out, stream=0):
         """d_out = self(d_in) + other(d_in_other) (dspfft_execute_sum2: one launch for two one-axis row REDFT01 plans on the same kernel)"""
         self._check(self._lib.dspfft_execute_sum2(self._h, other._h, d_in, d_in_other, d_out, stream or None))

@@ -4,14 +4,23 @@
  * (include/dspfft.h "the other scan methods on the device"): one fused masked-accumulate execution per output frame, no
  * PCIe traffic inside the loop.  The host-pointer drop-in of the same loop is host/scan_gpu.c.
  *
- *   scan_dev in.{ppm,pf} out.pf [step] [method]
+ *   scan_dev in.{ppm,pf} out.pf [step] [method] [--offset N] [--skip] [--invert] [--frames N]     (options anywhere)
  *     method: a prefix of horizontal vertical zigzag row column diagonal mirror box ibox radial iradial (scan_methods.c:581-591),
  *             magnitude[:qfactor] (scan_methods.c:240-296), file:<path> (scan_methods.c:393-410, either serialisation), or
  *             random[:seed] (scan_methods.c:210-228: the permutation is drawn on the host with libc rand(), as the tool draws it).
  *             evalxy / evali (scan_methods.c:186-201,333-391) need libavutil's expression evaluator and are not mirrored: write the order
  *             they would give to a file and pass file:<path>.
+ *   --offset N / -O N, --skip, --invert / -I, --frames N / -n N: scan.c:55-59,176-205,346-459, arithmetic and quirks included:
+ *     nframes = 0 or > limit/step becomes ceil(limit/step) (:347-348; limit/step with a remainder drops the last partial frame);
+ *     offset >= limit becomes limit - 1 (:385-386); unless --skip, ONE inverse adds the scan indices [0, offset) first (the fill,
+ *     :389-417; inverted: [limit - offset, limit)); the loop then runs FRAMES offset .. offset + nframes - 1 (:421), i.e. from scan index
+ *     offset * step, so with step > 1 the indices [offset, offset * step) are never added -- the reference's behaviour, kept; frames past
+ *     limit add nothing; --invert walks the scan backwards, index j = limit - 1 - s (:391,424).
+ *   The fill and every inverted frame are one dspfft_execute_masked_accumulate_range over the owner index (DC unmarked: the reference
+ *   clears it before every inverse, :406,445); box, and files whose indices share pixels, stamp those indices instead (the fill in
+ *   chunks of `step` indices under one reserved id, then one step on that id).
  * Output: the final `sum` image; on stderr the number of frames and max|sum - input| (0 up to rounding when the method visits
- * every pixel exactly once).
+ * every pixel exactly once and the whole scan is run).
  */
 #include <math.h>
 #include <stdint.h>
@@ -29,19 +38,36 @@
 #define HIP(x) do { if ((x) != hipSuccess) { fprintf(stderr, "HIP error at %s:%d\n", __FILE__, __LINE__); return 1; } } while (0)
 #define DSP(x) do { if (x) { fprintf(stderr, "dspfft: %s (%s:%d)\n", dspfft_last_error(), __FILE__, __LINE__); return 1; } } while (0)
 
+#define FILL_ID 0xFFFFFFFEu           /* the id the fill's pixels are stamped with (frame ids stay below limit + nframes) */
+
 int main(int argc, char *argv[])
 {
-	if (argc < 3) { fprintf(stderr, "usage: %s <in> <out.pf> [step] [method]\n", argv[0]); return 2; }
+	/* positional arguments in their order, the options anywhere */
+	const char *pos[4] = {NULL, NULL, NULL, NULL};
+	int npos = 0, skip = 0, invert = 0;
+	size_t offset = 0, nframes = 0;
+	for (int a = 1; a < argc; a++) {
+		const char *s = argv[a];
+		if ((!strcmp(s, "--offset") || !strcmp(s, "-O") || !strcmp(s, "--frames") || !strcmp(s, "-n")) && a + 1 < argc) {
+			const size_t v = strtoul(argv[++a], NULL, 10);
+			if (s[1] == 'O' || s[2] == 'o') offset = v; else nframes = v;
+		} else if (!strcmp(s, "--skip")) skip = 1;
+		else if (!strcmp(s, "--invert") || !strcmp(s, "-I")) invert = 1;
+		else if (s[0] == '-' && s[1]) { fprintf(stderr, "unknown option %s\n", s); return 2; }
+		else if (npos < 4) pos[npos++] = s;
+		else { fprintf(stderr, "too many arguments\n"); return 2; }
+	}
+	if (npos < 2) { fprintf(stderr, "usage: %s <in> <out.pf> [step] [method] [--offset N] [--skip] [--invert] [--frames N]\n", argv[0]); return 2; }
 	size_t width, height;
 	const int channels = 3;
 	float *pix;
-	if (read_image(argv[1], &width, &height, &pix)) { fprintf(stderr, "cannot read %s\n", argv[1]); return 1; }
-	const char *mname = argc > 4 ? argv[4] : "zigzag";
+	if (read_image(pos[0], &width, &height, &pix)) { fprintf(stderr, "cannot read %s\n", pos[0]); return 1; }
+	const char *mname = npos > 3 ? pos[3] : "zigzag";
 	const uint32_t w = (uint32_t)width, h = (uint32_t)height;
 	const size_t npix = width * height, n = npix * channels;
 
 	float *d_coeffs, *d_sum, *d_work;
-	uint32_t *d_ids;
+	uint32_t *d_ids, *d_index = NULL;       /* d_index: the owner index for the fill and inverted frames */
 	HIP(hipMalloc((void **)&d_coeffs, n * 4)); HIP(hipMalloc((void **)&d_sum, n * 4)); HIP(hipMalloc((void **)&d_work, n * 4));
 	HIP(hipMalloc((void **)&d_ids, npix * 4));
 	HIP(hipMemcpy(d_coeffs, pix, n * 4, hipMemcpyHostToDevice));
@@ -96,41 +122,66 @@ int main(int argc, char *argv[])
 		slots = dspfft_scan_coord_slots(method, w, h);
 		per_frame_lists = method == DSPFFT_SCAN_BOX;
 	}
-	size_t step = argc > 3 ? strtoul(argv[3], NULL, 10) : (limit + 31) / 32;
+	size_t step = npos > 2 ? strtoul(pos[2], NULL, 10) : (limit + 31) / 32;
 	if (!step) step = 1;
-	const size_t nframes = (limit + step - 1) / step;                                            /* scan.c:347-348 */
+	if (!nframes || nframes > limit / step) nframes = (limit + step - 1) / step;                  /* scan.c:347-348 */
+	if (offset >= limit) offset = limit - 1;                                                      /* scan.c:385-386 */
+	const int fill = !skip && offset > 0;
+	if (!per_frame_lists && (fill || invert)) {                                                   /* the owner index, DC unmarked */
+		HIP(hipMalloc((void **)&d_index, npix * 4));
+		if (method >= 0) DSP(dspfft_scan_owner_index(d_index, method, w, h, NULL));
+		else HIP(hipMemcpy(d_index, d_ids, npix * 4, hipMemcpyDeviceToDevice));                    /* magnitude / file: still the index */
+		HIP(hipMemset(d_index, 0xff, 4));
+	}
 	if (per_frame_lists) {
 		HIP(hipMalloc((void **)&d_lin, (size_t)step * (slots ? slots : 1) * 4));
 		HIP(hipMemset(d_ids, 0xff, npix * 4));
 	} else if (method >= 0) DSP(dspfft_scan_frame_ids(d_ids, method, w, h, step, NULL));
 	else DSP(dspfft_scan_index_to_frame_ids(d_ids, npix, step, NULL));                            /* magnitude / file: index -> frame */
 	/* owner ids that stay put over the frames: let the fused step skip the column tiles a frame does not touch (box restamps its ids) */
-	if (!per_frame_lists) DSP(dspfft_plan_scan_prepare(inv, d_ids, channels, NULL));
+	if (!per_frame_lists) DSP(dspfft_plan_scan_prepare(inv, invert ? d_index : d_ids, channels, NULL));
 
 	DSP(dspfft_broadcast_dc(d_sum, d_coeffs, npix, channels, NULL));                              /* scan.c:377-383 */
 	uint32_t *h_lin = per_frame_lists && method < 0 ? malloc((size_t)step * (slots ? slots : 1) * 4) : NULL;
-	for (size_t i = 0; i < nframes; i++) {                                                        /* scan.c:421-459 */
-		const size_t lo = i * step, hi = lo + step < limit ? lo + step : limit;
+	/* stamps d_ids[pixels of scan indices [a, b)] = id, at most `step` indices per list (the size of d_lin) */
+	#define STAMP(a, b, id) do { \
+		for (size_t c0 = (a); c0 < (b); c0 += step) { \
+			const size_t c1 = c0 + step < (b) ? c0 + step : (b); \
+			size_t cnt; \
+			if (method >= 0) { DSP(dspfft_scan_coords(d_lin, method, w, h, c0, c1 - c0, NULL)); cnt = (c1 - c0) * slots; } \
+			else { \
+				cnt = fl.offset[c1] - fl.offset[c0]; \
+				for (size_t k = 0; k < cnt; k++) h_lin[k] = (uint32_t)(fl.yx[fl.offset[c0] + k][0] * width + fl.yx[fl.offset[c0] + k][1]); \
+				HIP(hipMemcpy(d_lin, h_lin, cnt * 4, hipMemcpyHostToDevice)); \
+			} \
+			DSP(dspfft_scan_stamp(d_ids, d_lin, cnt, (id), NULL)); \
+		} \
+	} while (0)
+	if (fill) {                                                                                   /* scan.c:389-417 */
+		const size_t a = invert ? limit - offset : 0, b = invert ? limit : offset;
 		if (per_frame_lists) {
-			size_t cnt;
-			if (method >= 0) { DSP(dspfft_scan_coords(d_lin, method, w, h, lo, hi - lo, NULL)); cnt = (hi - lo) * slots; }
-			else {
-				cnt = fl.offset[hi] - fl.offset[lo];
-				for (size_t k = 0; k < cnt; k++) h_lin[k] = (uint32_t)(fl.yx[fl.offset[lo] + k][0] * width + fl.yx[fl.offset[lo] + k][1]);
-				HIP(hipMemcpy(d_lin, h_lin, cnt * 4, hipMemcpyHostToDevice));
-			}
-			DSP(dspfft_scan_stamp(d_ids, d_lin, cnt, (uint32_t)i, NULL));
-		}
-		DSP(dspfft_execute_masked_accumulate(inv, d_coeffs, d_work, d_sum, d_ids, (uint32_t)i, channels, NULL));
+			STAMP(a, b, FILL_ID);
+			DSP(dspfft_execute_masked_accumulate(inv, d_coeffs, d_work, d_sum, d_ids, FILL_ID, channels, NULL));
+		} else DSP(dspfft_execute_masked_accumulate_range(inv, d_coeffs, d_work, d_sum, d_index, (uint32_t)a, (uint32_t)b, channels, NULL));
 	}
+	for (size_t i = offset; i < offset + nframes; i++) {                                          /* scan.c:421-459 */
+		const size_t lo = i * step, hi = lo + step < limit ? lo + step : limit;
+		if (lo >= limit) continue;                       /* no scan index left: the frame adds nothing (the sum is emitted unchanged) */
+		const size_t a = invert ? limit - hi : lo, b = invert ? limit - lo : hi;                 /* scan.c:424 j = limit - 1 - s */
+		if (per_frame_lists) STAMP(a, b, (uint32_t)i);
+		if (invert && !per_frame_lists)
+			DSP(dspfft_execute_masked_accumulate_range(inv, d_coeffs, d_work, d_sum, d_index, (uint32_t)a, (uint32_t)b, channels, NULL));
+		else DSP(dspfft_execute_masked_accumulate(inv, d_coeffs, d_work, d_sum, d_ids, (uint32_t)i, channels, NULL));
+	}
+	#undef STAMP
 	float *sum = malloc(n * 4);
 	HIP(hipMemcpy(sum, d_sum, n * 4, hipMemcpyDeviceToHost));
 	double err = 0;
 	for (size_t j = 0; j < n; j++) { const double e = fabs((double)sum[j] - pix[j]); if (e > err) err = e; }
 	fprintf(stderr, "method %s: %zu scan indices, %zu frames of %zu, device-resident; max|sum-input| = %.3e\n", mname, (size_t)limit, nframes, step, err);
-	const int rc = write_pf(argv[2], width, height, sum);
+	const int rc = write_pf(pos[1], width, height, sum);
 	dspfft_destroy_plan(fwd); dspfft_destroy_plan(inv);
-	hipFree(d_coeffs); hipFree(d_sum); hipFree(d_work); hipFree(d_ids); hipFree(d_lin);
+	hipFree(d_coeffs); hipFree(d_sum); hipFree(d_work); hipFree(d_ids); hipFree(d_index); hipFree(d_lin);
 	free(sum); free(pix); free(h_lin); scan_order_list_free(&fl);
 	return rc;
 }

@@ -283,6 +283,20 @@ int dspfft_scan_scatter(float *d_recon, const float *d_coeffs, const uint32_t *d
  * one plan each); d_work then holds garbage in the skipped tiles, as scratch may. */
 int dspfft_execute_masked_accumulate(dspfft_plan plan, const float *d_in, float *d_work, float *d_acc,
                                      const uint32_t *d_ids, uint32_t id, int elems_per_id, void *hip_stream);
+/* The same step over a RANGE of owner ids:
+ *     d_acc += plan( d_in restricted to elements e with lo <= d_ids[e / elems_per_id] < hi )
+ * With an owner-index table (dspfft_scan_owner_index, or a magnitude / file index) one call adds every scan index of [lo, hi): scan's
+ * --offset fill (scan/scan.c:389-417), an inverted-order frame (:424), or the prefix a frame-range shard starts from (dist.py
+ * FrameShardedScan).  hi <= lo selects nothing.  The id 0xFFFFFFFF (the DC pixel, pixels no index owns) is never selected, whatever hi:
+ * the reference clears DC before every inverse (scan.c:406,445), so the caller's table need not mark it.  d_ids must not be NULL.
+ * A table prepared with dspfft_plan_scan_prepare is used as for one id; its 1- or 2-byte element ids saturate at 0xff / 0xffff, and both
+ * ends of the range are clamped to that value, which drops nothing (such a table exists only while every other id lies below it).
+ * The tile (min, max) skip of a prepared table applies to single ids only: a range reads the tiles' ids.
+ * dspfft_execute_masked_accumulate(..., id, ...) is this call on [id, id + 1), bit for bit. */
+int dspfft_execute_masked_accumulate_range(dspfft_plan plan, const float *d_in, float *d_work, float *d_acc,
+                                           const uint32_t *d_ids, uint32_t lo, uint32_t hi, int elems_per_id, void *hip_stream);
+int dspfft_execute_masked_accumulate_range_f64(dspfft_plan plan, const double *d_in, double *d_work, double *d_acc,
+                                               const uint32_t *d_ids, uint32_t lo, uint32_t hi, int elems_per_id, void *hip_stream);
 
 /* d_ids[y*w+x] = (zigzag scan index of (y,x)) / step -- the output frame (scan/scan.c:421-427) that
  * reconstructs coefficient (y,x); the DC pixel gets 0xFFFFFFFF (it is pre-added, scan.c:377-383,445). */
