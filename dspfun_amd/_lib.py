@@ -16,7 +16,7 @@ REDFT01, REDFT10 = 4, 5
 SYMBOLS = [
     "dspfft_plan_many_r2r", "dspfft_plan_r2r_2d", "dspfft_plan_set_scale", "dspfft_plan_set_axis_scale0",
     "dspfft_plan_many_r2r_f64", "dspfft_plan_set_scale_f64", "dspfft_plan_set_axis_scale0_f64", "dspfft_execute_f64", "dspfft_execute_masked_accumulate_f64", "dspfft_plan_scan_prepare", "dspfft_plan_set_input_window", "dspfft_plan_set_output_alternate", "dspfft_set_plan_effort", "dspfft_get_plan_effort",
-    "dspfft_plan_many_r2r_ordered", "dspfft_plan_guru_r2r", "dspfft_execute_roundtrip", "dspfft_execute_roundtrip_u8",
+    "dspfft_plan_many_r2r_ordered", "dspfft_plan_guru_r2r", "dspfft_execute_roundtrip", "dspfft_execute_roundtrip_u8", "dspfft_execute_roundtrip_u8_dither",
     "dspfft_execute", "dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
     "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
     "dspfft_last_error", "dspfft_version", "dspfft_set_thread_plan_effort", "dspfft_get_thread_plan_effort", "dspfft_fftw_sparse_uploads",
@@ -28,13 +28,18 @@ SYMBOLS = [
     "dspfft_zoom_last_error", "dspfft_zoomfft_create", "dspfft_zoomfft_work_floats", "dspfft_zoomfft_execute", "dspfft_zoomfft_destroy", "dspfft_zoomfft_last_error", "dspfft_zoomczt_create", "dspfft_zoomczt_work_floats", "dspfft_zoomczt_execute", "dspfft_zoomczt_destroy",
     "dspfft_applybasis_work_floats", "dspfft_applybasis_partsums",
     "dspfft_applybasis_work_floats_ex", "dspfft_applybasis_partsums_ex", "dspfft_applybasis_render",
-    "dspfft_motion_load_u8", "dspfft_motion_store_u8", "dspfft_motion_load_f32", "dspfft_motion_store_f32", "dspfft_motion_topn_work_bytes", "dspfft_motion_topn", "dspfft_motion_last_error",
+    "dspfft_motion_load_u8", "dspfft_motion_store_u8", "dspfft_motion_load_f32", "dspfft_motion_store_f32", "dspfft_motion_topn_work_bytes", "dspfft_motion_topn", "dspfft_motion_last_error", "dspfft_motion_dither_u8",
     "dspfft_spec_encode", "dspfft_ispec_decode", "dspfft_ispec_signmap", "dspfft_motion_filter", "dspfft_scan_pruned_accumulate", "dspfft_scan_pruned_work_floats", "dspfft_scan_pruned_accumulate_ws", "dspfft_pointwise_last_error",
 ]
 
 class IoDim(C.Structure):
     """dspfft_iodim (include/dspfft.h): extent, input stride, output stride in elements"""
     _fields_ = [("n", C.c_int), ("is_", C.c_int), ("os", C.c_int)]
+
+
+class DitherGeom(C.Structure):
+    """dspfft_dither_geom (include/dspfft.h)"""
+    _fields_ = [("n", C.c_int * 3), ("row_pitch", C.c_longlong), ("plane_pitch", C.c_longlong), ("nblocks", C.c_int * 3), ("block_step", C.c_longlong * 3)]
 
 
 class MotionFilterParams(C.Structure):
@@ -87,6 +92,7 @@ def bind(lib):
     lib.dspfft_plan_guru_r2r.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(IoDim), C.c_int, C.POINTER(IoDim), ip, C.c_int]
     lib.dspfft_execute_roundtrip.argtypes = [vp, vp, vp, vp, C.POINTER(MotionFilterParams), vp, vp]
     lib.dspfft_execute_roundtrip_u8.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), vp, vp]
+    lib.dspfft_execute_roundtrip_u8_dither.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.POINTER(MotionFilterParams), vp, vp]
     lib.dspfft_plan_set_scale_f64.argtypes = [vp, C.c_double]
     lib.dspfft_plan_set_axis_scale0_f64.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     lib.dspfft_execute_f64.argtypes = [vp, vp, vp, vp]
@@ -162,6 +168,7 @@ def bind(lib):
         lib.dspfft_motion_topn_work_bytes.argtypes = [C.c_size_t]
         lib.dspfft_motion_topn.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]
         lib.dspfft_motion_last_error.restype = C.c_char_p
+        lib.dspfft_motion_dither_u8.argtypes = [vp, vp, C.POINTER(DitherGeom), C.c_double, C.c_double, vp]
         lib.dspfft_scan_pruned_accumulate.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         lib.dspfft_scan_pruned_work_floats.restype = C.c_size_t
         lib.dspfft_scan_pruned_work_floats.argtypes = [C.c_int, C.c_int, C.c_int]

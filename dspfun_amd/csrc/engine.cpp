@@ -25,6 +25,11 @@
 
 using namespace dspfft;
 
+// motion_dither.hip's launcher (dspfft_motion_dither_u8's body).  Weak: the CPU emulation build of this file has no HIP kernels, the
+// reference is then null and the dithered roundtrip reports that it is not in the build.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g,
+                                                                                 double scalefactor, double normalization, void *stream, char *err, size_t errlen);
+
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
 {
@@ -1527,8 +1532,37 @@ int run_pass_u8(const dspfft_plan_s *pl, const Pass &P, const float *in, float *
 	return 0;
 }
 
+// motion's -d (dspfft_execute_roundtrip_u8_dither): the bytes come from the dither kernel (motion_dither.hip) instead of the last inverse pass
+struct Dither { uint8_t *out8; double sf, norm; };
+// the planes of a plan's output layout: its last two axes (rank 1: rows of their own), the first of three and the batch axes index planes
+int dither_geom_of(const dspfft_plan_s *p, dspfft_dither_geom &g)
+{
+	const int r = p->rank;
+	if (p->axes[r - 1].os != 1) return fail(-2, "dithered store: the contiguous axis must be the plan's last (planar layout)");
+	g.n[0] = r == 3 ? p->n[0] : 1; g.n[1] = r >= 2 ? p->n[r - 2] : 1; g.n[2] = p->n[r - 1];
+	g.row_pitch = r >= 2 ? p->axes[r - 2].os : p->n[r - 1];
+	g.plane_pitch = r == 3 ? p->axes[0].os : 0;
+	int k = 0;
+	for (int i = 0; i < 3; i++) { g.nblocks[i] = 1; g.block_step[i] = 0; }
+	for (const Dim &b : p->batches) {
+		if (b.n == 1) continue;
+		if (k == 3) return fail(-2, "dithered store: more than three batch axes");
+		g.nblocks[k] = b.n; g.block_step[k] = b.os; k++;
+	}
+	return 0;
+}
+int dither_store(const dspfft_plan_s *inv, const float *work, const Dither &dz, void *stream)
+{
+	dspfft_dither_geom g;
+	if (int rc = dither_geom_of(inv, g)) return rc;
+	char err[256] = "";
+	if (!dspfft_dither_launch) return fail(-3, "dithered 8-bit store: not in this build");
+	if (dspfft_dither_launch(dz.out8, work, &g, dz.sf, dz.norm, stream, err, sizeof err)) return fail(-4, "%s", err);
+	return 0;
+}
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
-                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice = true);
+                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice = true,
+                   const Dither *dither = nullptr);
 
 // ---- a clip of frames in slices (motion's per-frame blocks, motion/motion.c:591,613-615: the frames are independent) ----
 // The three launches of the 8-bit roundtrip move the clip's float intermediate through HBM four times (2.1 GB for config 5's luma plane).  Walked
@@ -1576,7 +1610,7 @@ dspfft_plan_s *slice_plan(const dspfft_plan_s *of, int frames)
 
 // returns 1 when the clip was run in slices, 0 when this call does not qualify (the caller runs it whole), < 0 on error
 int roundtrip_sliced(dspfft_plan fwd, dspfft_plan inv, float *d_work, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
-                     const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream)
+                     const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, const Dither *dither)
 {
 	static const int nstreams = []() { const char *e = getenv("DSPFFT_RT_STREAMS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v > 2 ? 2 : v; }();
 	const int S = slice_frames(fwd, inv, fp, nstreams);
@@ -1614,16 +1648,20 @@ int roundtrip_sliced(dspfft_plan fwd, dspfft_plan inv, float *d_work, const uint
 		const bool last = total - f0 < S;
 		void *st = (two && (k & 1)) ? r->side : stream;
 		float *work = d_work + ((two && (k & 1)) ? (long long)S * fwk : 0);
-		if (int rc = roundtrip_core(last ? r->fwd_rem : r->fwd, last ? r->inv_rem : r->inv, nullptr, work, d_in8 + (long long)f0 * fin, d_out8 + (long long)f0 * fout, mul8,
-		                            fp, d_coeffs_coded, st, false)) return rc;
+		// dithered: each slice's planes (whole frames) are dithered on the slice's stream before its work area is reused
+		Dither ds;
+		if (dither) { ds = *dither; ds.out8 += (long long)f0 * fout; }
+		if (int rc = roundtrip_core(last ? r->fwd_rem : r->fwd, last ? r->inv_rem : r->inv, nullptr, work, d_in8 + (long long)f0 * fin,
+		                            d_out8 ? d_out8 + (long long)f0 * fout : nullptr, mul8, fp, d_coeffs_coded, st, false, dither ? &ds : nullptr)) return rc;
 	}
 	if (two && (be_event_record(r->ev_join, r->side) || be_stream_wait_event(stream, r->ev_join))) return fail(-4, "stream join failed");
 	return 1;
 }
 
-// d_in8 / d_out8 non-NULL: 8-bit samples at the two ends (dspfft_execute_roundtrip_u8), d_out is then the float work buffer
+// d_in8 / d_out8 non-NULL: 8-bit samples at the two ends (dspfft_execute_roundtrip_u8), d_out is then the float work buffer.
+// dither non-NULL (d_out8 NULL): the inverse transform ends in d_out as floats and the dither kernel stores dither->out8 from there.
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
-                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice)
+                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice, const Dither *dither)
 {
 	if (!fwd || !inv || !(d_in || d_in8) || !d_out) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
@@ -1685,7 +1723,7 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 			block_scales(fwd, a.f); block_scales(inv, a.i);
 			a.filt = mf; a.coded = d_coeffs_coded;
 			if (int rc = be_launch_block_roundtrip(a, fwd->blk_nwg, fwd->blk_lds, stream)) return fail(-4, "kernel launch failed (fused block roundtrip): backend code %d", rc);
-			return 0;
+			return dither ? dither_store(inv, d_out, *dither, stream) : 0;
 		}
 	}
 	// the standalone filter finds a coefficient's position from its offset in a block-major embedding (minbuf_hw, block_depth); the
@@ -1709,7 +1747,7 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 		for (size_t i = 0; i < ni; i++)
 			if (int rc = run_pass<float>(inv, inv->passes[i], (const float *)d_out, d_out, i + 1 == ni, stream)) return rc;
 		if (d_out8 && be_region_f32_to_u8(d_out8, d_out, mul8, ni3, sw3, sw3, stream)) return fail(-4, "launch failed");
-		return 0;
+		return dither ? dither_store(inv, d_out, *dither, stream) : 0;
 	}
 	if (d_in8 || d_out8) {
 		// the 8-bit buffers share the plans' element layout; the unfused conversions below walk whole spans
@@ -1730,9 +1768,9 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 			d_in = d_out; d_in8 = nullptr;
 		}
 	}
-	if (may_slice && d_in8 && d_out8 && pass_has_u8(fwd, fwd->passes[0]) && pass_has_u8(inv, inv->passes[ni - 1]) && F.axis == I.axis &&
+	if (may_slice && d_in8 && (d_out8 || dither) && pass_has_u8(fwd, fwd->passes[0]) && pass_has_u8(inv, inv->passes[ni - 1]) && F.axis == I.axis &&
 	    (15u & (uintptr_t)d_out) == 0 && !(getenv("DSPFFT_NO_FUSED_ROUNDTRIP") && *getenv("DSPFFT_NO_FUSED_ROUNDTRIP") == '1')) {
-		const int rc = roundtrip_sliced(fwd, inv, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream);
+		const int rc = roundtrip_sliced(fwd, inv, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream, dither);
 		if (rc) return rc < 0 ? rc : 0;
 	}
 	for (size_t i = 0; i + 1 < nf; i++) {
@@ -1776,7 +1814,7 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 		if (int rc = run_pass<float>(inv, P, (const float *)d_out, d_out, i + 1 == ni, stream)) return rc;
 	}
 	if (d_out8 && be_f32_to_u8(d_out8, d_out, mul8, (uint64_t)span, stream)) return fail(-4, "launch failed");    // no fused store: one sweep
-	return 0;
+	return dither ? dither_store(inv, d_out, *dither, stream) : 0;
 }
 }  // namespace
 
@@ -1792,6 +1830,20 @@ extern "C" int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, con
 {
 	if (!d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
 	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream);
+}
+
+extern "C" int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
+                                                  double scalefactor, double normalization, const dspfft_motion_filter_params *fp,
+                                                  unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (!fwd || !inv || !d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
+	if (fwd->f64 || inv->f64) return fail(-1, "the dithered roundtrip takes f32 plans");
+	if (!dspfft_dither_launch) return fail(-3, "dithered 8-bit store: not in this build (the dither kernel is HIP-only, motion_dither.hip)");
+	if (!(scalefactor > 0) || !(normalization > 0)) return fail(-1, "dither: scalefactor and normalization must be > 0");
+	dspfft_dither_geom g;
+	if (int rc = dither_geom_of(inv, g)) return rc;
+	const Dither dz = {d_out, scalefactor, normalization};
+	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, nullptr, 1.0, fp, d_coeffs_coded, stream, true, &dz);
 }
 
 extern "C" int dspfft_scan_zigzag_frame_ids(uint32_t *d_ids, uint32_t w, uint32_t h, uint64_t step, void *s)

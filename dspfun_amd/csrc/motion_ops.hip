@@ -103,6 +103,7 @@ size_t scan_temp(size_t n)
 }  // namespace
 
 extern "C" const char *dspfft_motion_last_error(void) { return g_merr; }
+extern "C" __attribute__((visibility("hidden"))) int dspfft_motion_set_error(const char *m) { return mbad(m); }   // (motion_dither.hip)
 
 extern "C" int dspfft_motion_load_u8(float *d_coeffs, const uint8_t *d_pix, const int n[3], const int minbuf_hw[2], int ispec_mode, double ic, double normalization, void *stream)
 {

@@ -191,6 +191,14 @@ class Plan:
         self._check(self._lib.dspfft_execute_roundtrip_u8(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
                                                           C.byref(fp) if fp is not None else None, C.c_void_p(d_coded or None), C.c_void_p(stream)))
 
+    def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0):
+        """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
+        Floyd-Steinberg dithered store of them (pel = value * scalefactor * normalization * normalization), plane by plane over inv's extents"""
+        fp = self._filter_params(filter)
+        self._check(self._lib.dspfft_execute_roundtrip_u8_dither(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work),
+                                                                 float(scalefactor), float(normalization), C.byref(fp) if fp is not None else None,
+                                                                 C.c_void_p(d_coded or None), C.c_void_p(stream)))
+
     def describe(self):
         buf = C.create_string_buffer(4096)
         self._check(self._lib.dspfft_plan_describe(self._h, buf, len(buf)))
@@ -214,6 +222,22 @@ class Plan:
     def _check(self, rc):
         if rc:
             raise DspfftError(self._lib.dspfft_last_error().decode())
+
+
+def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nblocks=(1, 1, 1), block_step=(0, 0, 0), scalefactor=1.0,
+                     normalization=1.0, stream=0, lib=None):
+    """dspfft_motion_dither_u8: motion.c:756-788 with -d over the {d, h, w} = n planes of every block (element (b, z, y, x) at
+    sum(b_i block_step_i) + z plane_pitch + y row_pitch + x in both buffers); d_coeffs is only read"""
+    lib = lib or _lib.load()
+    n = [int(v) for v in n]
+    g = _lib.DitherGeom()
+    g.n[:] = n
+    g.row_pitch = n[2] if row_pitch is None else int(row_pitch)
+    g.plane_pitch = n[1] * g.row_pitch if plane_pitch is None else int(plane_pitch)
+    g.nblocks[:] = [int(v) for v in nblocks]
+    g.block_step[:] = [int(v) for v in block_step]
+    if lib.dspfft_motion_dither_u8(C.c_void_p(d_pix), C.c_void_p(d_coeffs), C.byref(g), float(scalefactor), float(normalization), C.c_void_p(stream)):
+        raise DspfftError(lib.dspfft_motion_last_error().decode())
 
 
 class Stream:

@@ -247,6 +247,15 @@ int dspfft_execute_roundtrip(dspfft_plan fwd, dspfft_plan inv, const float *d_in
  * identical and dense. */
 int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
                                 const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
+/* dspfft_execute_roundtrip_u8 with motion's -d: the final 8-bit store replaced by the dithered one (dspfft_motion_dither_u8 below, over the
+ * inverse plan's extents -- `scaled` -- plane by plane: the last two transformed axes are the plane, the first of three and the batch axes
+ * index planes; the contiguous axis must be the last).  Every path of the undithered call is taken alike (fused 8-bit load, fused column
+ * roundtrip, a clip in slices, one 3-D block, scaled != block, the fused small-block kernel); the last inverse pass writes float into d_work
+ * and the dither kernel writes the bytes.  d_work then holds the inverse transform's output (what was dithered), untouched by the dither.
+ * d_coeffs_coded is counted as by the undithered call.  Same precision contract as dspfft_motion_dither_u8.  Single precision plans only. */
+int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
+                                       double scalefactor, double normalization, const dspfft_motion_filter_params *filter,
+                                       unsigned long long *d_coeffs_coded, void *hip_stream);
 
 /* Replaces fftw(destroy_plan). */
 void dspfft_destroy_plan(dspfft_plan plan);
@@ -356,6 +365,27 @@ int dspfft_motion_store_u8(uint8_t *d_pix, const float *d_coeffs, const int n[3]
 int dspfft_motion_load_f32(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], int ispec_mode, double ic, double normalization, void *hip_stream);
 int dspfft_motion_store_f32(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], int spec_mode,
                             double scalefactor, double normalization, double c, void *hip_stream);
+/* motion.c:756-788 with -d / --dither (spec none, 8-bit pixels, !linear): the 8-bit store with 2-D Floyd-Steinberg error diffusion, plane
+ * by plane (the z planes of a block are independent, and so are blocks).  Per pixel, in raster order: pel = c * scalefactor * normalization,
+ * pel *= normalization, byte = clamp + lround, dp = c - byte / (normalization^2 scalefactor), and dp * 7/16, 3/16, 5/16, 1/16 go into the
+ * right, lower-left, lower and lower-right neighbours, each `+=` rounding to float -- so the order in which a pixel receives them (1/16, 5/16,
+ * 3/16 from the row above, then 7/16 from the left) is part of the result and is kept.
+ * Element (block b0,b1,b2; plane z; row y; column x) is at b0 block_step[0] + b1 block_step[1] + b2 block_step[2] + z plane_pitch +
+ * y row_pitch + x, in d_pix and d_coeffs alike.  Covers a stack of frames (per-frame blocks: n = {1,h,w}, nblocks = {frames,1,1}), one 3-D
+ * block (n = {d,h,w}), small blocks as a block-major stack or lying in a volume (one nblocks / block_step per axis).
+ * d_coeffs is READ, never written (the reference diffuses into its coefficient buffer, which nothing reads afterwards).
+ * Precision: intermediates in double, in the reference's operation order, nothing contracted into an FMA: byte-identical to the reference's
+ * lines built with COEFF_PRECISION=F INTERMEDIATE_PRECISION=D.  Against the tool's default long double build (=L) the bytes CANNOT match in
+ * general: error diffusion is chaotic, one last-bit difference flips a rounding and the pattern downstream follows -- +-1 on some per cent of
+ * the pixels of a whole frame, 8x8 block means within 0.1 (tests/test_motion_dither_cpu.py pins both bars).
+ * Planes up to 64 wide and 1024 samples run one lane per plane; larger ones a wavefront over a workgroup (rows up to about 9000 samples). */
+typedef struct {
+	int n[3];                               /* scaled block extent {d, h, w}; dithered plane by plane */
+	long long row_pitch, plane_pitch;       /* elements, shared by d_pix and d_coeffs */
+	int nblocks[3];                         /* blocks along {d, h, w} (any three batch axes); {1,1,1} for one block */
+	long long block_step[3];                /* elements between neighbouring blocks along each of them */
+} dspfft_dither_geom;
+int dspfft_motion_dither_u8(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor, double normalization, void *hip_stream);
 /* motion.c:652-668 (--coeff-limit): keep the `keep` coefficients of largest magnitude among d_coeffs[0 .. count), zero the rest.
  * Radix select on the device (four histogram passes over the bits of |c|, no sort).  Ties at the threshold: the reference's choice
  * depends on qsort; here the earliest in buffer order are kept -- documented, deterministic. */
