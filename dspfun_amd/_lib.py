@@ -26,6 +26,8 @@ SYMBOLS = [
     "dspfft_u8_to_f32", "dspfft_f32_to_u8",
     "dspfft_zoom_ncomponents", "dspfft_zoom_basis", "dspfft_zoom_work_floats", "dspfft_zoom_product", "dspfft_gemm_nt_f32",
     "dspfft_zoom_last_error", "dspfft_zoomfft_create", "dspfft_zoomfft_work_floats", "dspfft_zoomfft_execute", "dspfft_zoomfft_destroy", "dspfft_zoomfft_last_error", "dspfft_zoomczt_create", "dspfft_zoomczt_work_floats", "dspfft_zoomczt_execute", "dspfft_zoomczt_destroy",
+    "dspfft_scanframes_create", "dspfft_scanframes_frame_floats", "dspfft_scanframes_begin", "dspfft_scanframes_mark_range", "dspfft_scanframes_mark_coords",
+    "dspfft_scanframes_compose", "dspfft_scanframes_parity", "dspfft_scanframes_destroy",
     "dspfft_applybasis_work_floats", "dspfft_applybasis_partsums",
     "dspfft_applybasis_work_floats_ex", "dspfft_applybasis_partsums_ex", "dspfft_applybasis_render",
     "dspfft_motion_load_u8", "dspfft_motion_store_u8", "dspfft_motion_load_f32", "dspfft_motion_store_f32", "dspfft_motion_topn_work_bytes", "dspfft_motion_topn", "dspfft_motion_last_error", "dspfft_motion_dither_u8",
@@ -40,6 +42,12 @@ class IoDim(C.Structure):
 class DitherGeom(C.Structure):
     """dspfft_dither_geom (include/dspfft.h)"""
     _fields_ = [("n", C.c_int * 3), ("row_pitch", C.c_longlong), ("plane_pitch", C.c_longlong), ("nblocks", C.c_int * 3), ("block_step", C.c_longlong * 3)]
+
+
+class ScanFrameOpts(C.Structure):
+    """dspfft_scan_frame_opts (include/dspfft.h)"""
+    _fields_ = [("visualize", C.c_int), ("spectrogram", C.c_int), ("intermediates", C.c_int), ("max_intermediates", C.c_int),
+                ("spec_gain", C.c_double), ("spec_scaletype", C.c_int), ("spec_signtype", C.c_int), ("parity_depth", C.c_int)]
 
 
 class MotionFilterParams(C.Structure):
@@ -134,6 +142,16 @@ def bind(lib):
     lib.dspfft_broadcast_dc.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
     lib.dspfft_u8_to_f32.argtypes = [vp, vp, C.c_uint64, vp]
     lib.dspfft_f32_to_u8.argtypes = [vp, vp, C.c_double, C.c_uint64, vp]
+    lib.dspfft_scanframes_create.argtypes = [C.POINTER(vp), C.c_uint32, C.c_uint32, C.POINTER(ScanFrameOpts)]
+    lib.dspfft_scanframes_frame_floats.restype = C.c_size_t
+    lib.dspfft_scanframes_frame_floats.argtypes = [vp]
+    lib.dspfft_scanframes_begin.argtypes = [vp, vp, vp, vp]
+    lib.dspfft_scanframes_mark_range.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp]
+    lib.dspfft_scanframes_mark_coords.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_int, vp]
+    lib.dspfft_scanframes_compose.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
+    lib.dspfft_scanframes_parity.argtypes = [vp, C.POINTER(C.c_uint64), vp]
+    lib.dspfft_scanframes_destroy.argtypes = [vp]
+    lib.dspfft_scanframes_destroy.restype = None
     if hasattr(lib, "dspfft_zoom_product"):      # HIP-only entry points (absent from the CPU emulation used in tests)
         lib.dspfft_zoom_ncomponents.restype = C.c_size_t
         lib.dspfft_zoom_ncomponents.argtypes = [C.c_double, C.c_double, C.c_size_t]

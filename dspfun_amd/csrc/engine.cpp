@@ -22,6 +22,7 @@
 
 #include "../../include/dspfft.h"
 #include "backend.h"
+#include "scan_frame_core.h"
 
 using namespace dspfft;
 
@@ -29,6 +30,9 @@ using namespace dspfft;
 // reference is then null and the dithered roundtrip reports that it is not in the build.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g,
                                                                                  double scalefactor, double normalization, void *stream, char *err, size_t errlen);
+
+// scan_frame.hip's launcher (the dspfft_scanframes_* bodies).  Weak, as dspfft_dither_launch: the CPU emulation build reports "not in this build".
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_scanframes_launch(dspfft::SfOp *o, char *err, size_t errlen);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -2145,4 +2149,154 @@ extern "C" int dspfft_f32_to_u8(uint8_t *d, const float *src, double mul, uint64
 {
 	if (!d || !src) return fail(-1, "bad arguments");
 	return be_f32_to_u8(d, src, mul, len, s) ? fail(-4, "launch failed") : 0;
+}
+
+// ---- scan's output frames (include/dspfft.h "scan's output frames on the device"; kernels in scan_frame.hip) ----
+struct dspfft_scanframes_s {
+	dspfft_scan_frame_opts o;
+	uint32_t w, h;
+	SfState *state;
+	void *partials;
+	uint32_t *flags;
+	uint32_t *saved;                        // the last current coordinate list (bottom-right marks to clear)
+	uint64_t saved_cap, saved_n;
+	int prev;                               // what the last current mark lit: 0 nothing, 1 a range of prev_owner, 2 the saved list
+	uint32_t prev_lo, prev_hi;
+	const uint32_t *prev_owner;
+};
+namespace {
+SfOp sf_op(dspfft_scanframes sf, int op, void *stream)
+{
+	SfOp o;
+	memset(&o, 0, sizeof o);
+	o.op = op; o.w = sf->w; o.h = sf->h;
+	o.visualize = sf->o.visualize; o.spectrogram = sf->o.spectrogram; o.intermediates = sf->o.intermediates;
+	o.max_intermediates = sf->o.max_intermediates; o.parity_depth = sf->o.parity_depth;
+	o.scaletype = sf->o.spec_scaletype; o.signtype = sf->o.spec_signtype; o.gain = sf->o.spec_gain;
+	o.state = sf->state; o.partials = sf->partials; o.flags = sf->flags; o.stream = stream;
+	return o;
+}
+int sf_run(SfOp &o)
+{
+	char err[256] = "";
+	if (!dspfft_scanframes_launch) return fail(-3, "scan frames: not in this build (the kernels are HIP-only, scan_frame.hip)");
+	return dspfft_scanframes_launch(&o, err, sizeof err) ? fail(-4, "%s", err) : 0;
+}
+// clears the bottom-right marks of the last current call (before the next one lights its own), unless `owner` can do it in its own pass
+int sf_clear_prev(dspfft_scanframes sf, float *frame, const uint32_t *owner, void *stream)
+{
+	if (sf->prev == 2) {
+		SfOp o = sf_op(sf, SF_OP_MARK_COORDS, stream);
+		o.frame = frame; o.lin = sf->saved; o.nslots = sf->saved_n;
+		if (int rc = sf_run(o)) return rc;
+	} else if (sf->prev == 1 && sf->prev_owner != owner) {
+		SfOp o = sf_op(sf, SF_OP_MARK_RANGE, stream);
+		o.frame = frame; o.owner = sf->prev_owner; o.clo = sf->prev_lo; o.chi = sf->prev_hi; o.bottom = 1;
+		if (int rc = sf_run(o)) return rc;
+	}
+	if (sf->prev != 1 || sf->prev_owner != owner) sf->prev = 0;
+	return 0;
+}
+}  // namespace
+
+extern "C" int dspfft_scanframes_create(dspfft_scanframes *out, uint32_t w, uint32_t h, const dspfft_scan_frame_opts *opts)
+{
+	if (!out || !opts || !w || !h) return fail(-1, "scan frames: bad arguments");
+	*out = nullptr;
+	if ((uint64_t)w * h > 0xfffffffeull) return fail(-1, "scan frames: image too large for 32-bit pixel indices");
+	dspfft_scan_frame_opts o = *opts;
+	if (o.spec_scaletype < SF_SCALE_NONE || o.spec_scaletype > SF_SCALE_LOG) return fail(-1, "scan frames: spec_scaletype must be 0..2");
+	if (o.spec_signtype < SF_SIGN_NONE || o.spec_signtype > SF_SIGN_SATURATE) return fail(-1, "scan frames: spec_signtype must be 0..3");
+	if (o.parity_depth < 0 || (o.parity_depth > 16 && o.parity_depth != 32)) return fail(-1, "scan frames: parity_depth must be 0, 1..16 or 32");
+	if (!isfinite(o.spec_gain)) return fail(-1, "scan frames: spec_gain must be finite");
+	o.visualize = o.visualize || o.spectrogram; o.spectrogram = !!o.spectrogram; o.visualize = !!o.visualize;       // scan.c:179-180: -s implies -v
+	o.intermediates = o.intermediates || o.max_intermediates; o.intermediates = !!o.intermediates;                   // scan.c:186: -M implies -i
+	o.max_intermediates = !!o.max_intermediates;
+	if (o.spec_gain == 0) o.spec_gain = sf_default_gain(w, h);                                                        // scan.c:367-368
+	dspfft_scanframes sf = new dspfft_scanframes_s();
+	sf->o = o; sf->w = w; sf->h = h;
+	if (dspfft_scanframes_launch) {                          // without the kernels (CPU emulation build) every later call reports it
+		SfOp a = sf_op(sf, SF_OP_ALLOC, nullptr);
+		if (int rc = sf_run(a)) { delete sf; return rc; }
+		sf->state = a.state; sf->partials = a.partials; sf->flags = a.flags;
+	}
+	*out = sf;
+	return 0;
+}
+extern "C" size_t dspfft_scanframes_frame_floats(dspfft_scanframes sf)
+{
+	if (!sf) return 0;
+	return 3ull * sf->w * (1 + sf->o.visualize) * sf->h * (1 + sf->o.intermediates);
+}
+extern "C" int dspfft_scanframes_begin(dspfft_scanframes sf, float *d_frame, const float *d_coeffs, void *stream)
+{
+	if (!sf || !d_frame || !d_coeffs) return fail(-1, "scan frames: bad arguments");
+	SfOp o = sf_op(sf, SF_OP_BEGIN, stream);
+	o.frame = d_frame; o.coeffs = d_coeffs;
+	sf->prev = 0;
+	return sf_run(o);
+}
+extern "C" int dspfft_scanframes_mark_range(dspfft_scanframes sf, float *d_frame, const float *d_coeffs, const uint32_t *d_owner, uint32_t lo, uint32_t hi,
+                                            int current, void *stream)
+{
+	if (!sf || !d_frame || !d_coeffs || !d_owner || lo > hi) return fail(-1, "scan frames: bad arguments");
+	if (!sf->o.visualize) return 0;                          // scan.c:397,432: nothing lit without -v
+	const bool bottom = current && sf->o.intermediates;
+	SfOp o = sf_op(sf, SF_OP_MARK_RANGE, stream);
+	o.frame = d_frame; o.coeffs = d_coeffs; o.owner = d_owner; o.lo = lo; o.hi = hi; o.top = 1; o.bottom = bottom;
+	if (bottom) {
+		if (int rc = sf_clear_prev(sf, d_frame, d_owner, stream)) return rc;
+		if (sf->prev == 1) { o.clo = sf->prev_lo; o.chi = sf->prev_hi; }
+	}
+	if (int rc = sf_run(o)) return rc;
+	if (bottom) { sf->prev = 1; sf->prev_lo = lo; sf->prev_hi = hi; sf->prev_owner = d_owner; }
+	return 0;
+}
+extern "C" int dspfft_scanframes_mark_coords(dspfft_scanframes sf, float *d_frame, const float *d_coeffs, const uint32_t *d_lin, uint64_t nslots,
+                                             int current, void *stream)
+{
+	if (!sf || !d_frame || !d_coeffs || (!d_lin && nslots)) return fail(-1, "scan frames: bad arguments");
+	if (!sf->o.visualize) return 0;
+	const bool bottom = current && sf->o.intermediates;
+	if (bottom) {
+		if (int rc = sf_clear_prev(sf, d_frame, nullptr, stream)) return rc;
+	}
+	SfOp o = sf_op(sf, SF_OP_MARK_COORDS, stream);
+	o.frame = d_frame; o.coeffs = d_coeffs; o.lin = d_lin; o.nslots = nslots; o.top = 1; o.bottom = bottom;
+	if (int rc = sf_run(o)) return rc;
+	if (bottom) {
+		SfOp c = sf_op(sf, SF_OP_SAVE_COORDS, stream);
+		c.lin = d_lin; c.nslots = nslots; c.saved = &sf->saved; c.saved_cap = &sf->saved_cap;
+		if (int rc = sf_run(c)) { sf->prev = 0; return rc; }
+		sf->prev = 2; sf->saved_n = nslots;
+	}
+	return 0;
+}
+extern "C" int dspfft_scanframes_compose(dspfft_scanframes sf, float *d_frame, float *d_sum, float *d_image, const float *d_coeffs, const float *d_original,
+                                         uint64_t frame, void *stream)
+{
+	if (!sf || !d_frame || !d_sum || !d_coeffs) return fail(-1, "scan frames: bad arguments");
+	if (sf->o.intermediates && !d_image) return fail(-1, "scan frames: -i needs this frame's image (d_image)");
+	if (sf->o.parity_depth && !d_original) return fail(-1, "scan frames: -P needs the original image (d_original)");
+	SfOp o = sf_op(sf, SF_OP_COMPOSE, stream);
+	o.frame = d_frame; o.sum = d_sum; o.image = d_image; o.coeffs = d_coeffs; o.original = sf->o.parity_depth ? d_original : nullptr; o.frame_no = frame;
+	return sf_run(o);
+}
+extern "C" int dspfft_scanframes_parity(dspfft_scanframes sf, uint64_t *first_frame, void *stream)
+{
+	if (!sf || !first_frame) return fail(-1, "scan frames: bad arguments");
+	if (!sf->o.parity_depth) return fail(-1, "scan frames: parity is not measured (parity_depth 0)");
+	SfOp o = sf_op(sf, SF_OP_PARITY, stream);
+	o.parity_out = first_frame;
+	return sf_run(o);
+}
+extern "C" void dspfft_scanframes_destroy(dspfft_scanframes sf)
+{
+	if (!sf) return;
+	if (dspfft_scanframes_launch) {
+		SfOp o = sf_op(sf, SF_OP_FREE, nullptr);
+		o.saved = &sf->saved;
+		sf_run(o);
+	}
+	delete sf;
 }

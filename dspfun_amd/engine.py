@@ -240,6 +240,90 @@ def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nbloc
         raise DspfftError(lib.dspfft_motion_last_error().decode())
 
 
+SPEC_SCALES = {"none": 0, "linear": 1, "log": 2}
+SPEC_SIGNS = {"none": 0, "abs": 1, "shift": 2, "saturate": 3}
+
+
+class ScanFrames:
+    """dspfft_scanframes: scan's output frames composed on the device (scan/scan.c:366-536).  Takes torch device tensors (float32 HWC
+    images, uint32 owner / coordinate tables, the float32 frame of frame_floats elements); every failure raises DspfftError.
+    Options as scan's: visualize (-v), spectrogram (-s, implies -v), intermediates (-i), max_intermediates (-M, implies -i),
+    spec_gain (--spec-gain, 0: the default), spec_scale / spec_sign (--spec-opts scale= / sign=), parity_depth (-P: 8, 16 or 32)."""
+
+    def __init__(self, w, h, visualize=False, spectrogram=False, intermediates=False, max_intermediates=False, spec_gain=0.0,
+                 spec_scale="none", spec_sign="none", parity_depth=0, lib=None):
+        self._lib = lib or _lib.load()
+        self._h = None
+        o = _lib.ScanFrameOpts(int(bool(visualize)), int(bool(spectrogram)), int(bool(intermediates)), int(bool(max_intermediates)), float(spec_gain),
+                               SPEC_SCALES[spec_scale] if isinstance(spec_scale, str) else int(spec_scale),
+                               SPEC_SIGNS[spec_sign] if isinstance(spec_sign, str) else int(spec_sign), int(parity_depth))
+        h_ = C.c_void_p()
+        self._check(self._lib.dspfft_scanframes_create(C.byref(h_), int(w), int(h), C.byref(o)))
+        self._h = h_
+        self.w, self.h = int(w), int(h)
+        self.visualize = bool(visualize or spectrogram)
+        self.intermediates = bool(intermediates or max_intermediates)
+
+    @property
+    def shape(self):
+        """(3, H', W'): the frame's G, B, R planes"""
+        return 3, self.h * (1 + self.intermediates), self.w * (1 + self.visualize)
+
+    @property
+    def frame_floats(self):
+        return int(self._lib.dspfft_scanframes_frame_floats(self._h))
+
+    def begin(self, frame, coeffs, stream=0):
+        self._check(self._lib.dspfft_scanframes_begin(self._h, _ptr(frame), _ptr(coeffs), C.c_void_p(stream)))
+
+    def mark_range(self, frame, coeffs, owner, lo, hi, current, stream=0):
+        self._check(self._lib.dspfft_scanframes_mark_range(self._h, _ptr(frame), _ptr(coeffs), _ptr(owner), int(lo), int(hi), int(bool(current)),
+                                                           C.c_void_p(stream)))
+
+    def mark_coords(self, frame, coeffs, lin, nslots=None, current=False, stream=0):
+        n = lin.numel() if nslots is None else int(nslots)
+        self._check(self._lib.dspfft_scanframes_mark_coords(self._h, _ptr(frame), _ptr(coeffs), _ptr(lin), n, int(bool(current)), C.c_void_p(stream)))
+
+    def compose(self, frame, sum_, image, coeffs, original, frame_no, stream=0):
+        self._check(self._lib.dspfft_scanframes_compose(self._h, _ptr(frame), _ptr(sum_), _ptr(image), _ptr(coeffs), _ptr(original), int(frame_no),
+                                                        C.c_void_p(stream)))
+
+    def parity(self, stream=0):
+        """the first frame at parity, or None (synchronises the stream)"""
+        v = C.c_uint64()
+        self._check(self._lib.dspfft_scanframes_parity(self._h, C.byref(v), C.c_void_p(stream)))
+        return None if v.value == 2 ** 64 - 1 else int(v.value)
+
+    def destroy(self):
+        if self._h:
+            self._lib.dspfft_scanframes_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise DspfftError(self._lib.dspfft_last_error().decode())
+
+
+def _ptr(t):
+    """a torch tensor, a raw device address or None -> c_void_p"""
+    if t is None:
+        return None
+    return C.c_void_p(t if isinstance(t, int) else t.data_ptr())
+
+
+def scan_frame_rgb(frame, w, h, visualize=False, intermediates=False):
+    """a frame (flat float32 tensor or array, G, B, R planes as dspfft_scanframes writes them) as [3, H', W'] in R, G, B order.  The planes
+    are reshaped views; reordering them takes one gather (a copy: no stride maps 0, 1, 2 to planes 2, 0, 1)."""
+    fw, fh = w * (1 + bool(visualize)), h * (1 + bool(intermediates))
+    return frame.reshape(3, fh, fw)[[2, 0, 1]]
+
+
 class Stream:
     """A HIP stream of the library's own (dspfft_stream_create: hipStreamNonBlocking).  `handle` is what execute / Batch take."""
 

@@ -19,8 +19,15 @@
  *   The fill and every inverted frame are one dspfft_execute_masked_accumulate_range over the owner index (DC unmarked: the reference
  *   clears it before every inverse, :406,445); box, and files whose indices share pixels, stamp those indices instead (the fill in
  *   chunks of `step` indices under one reserved id, then one step on that id).
+ *   -v / --visualize, -s / --spectrogram, --spec-gain G, --spec-opts k=v:..., -i / --intermediates, -M / --max-intermediates,
+ *   -P / --measure-parity (scan.c:41-76,176-215, -s implies -v, -M implies -i): the output frames of scan.c:366-536 composed on the device
+ *     (include/dspfft.h "scan's output frames"); a frame for EVERY i in [offset, offset + nframes), past the limit included.  -P prints
+ *     the reference's message (depth 8 for P6 input, 32 for PF).  -g / --linear is refused (needs a colourspace transform).
+ *   --video PATH: every frame as raw gbrpf32le, concatenated (ffmpeg -f rawvideo -pix_fmt gbrpf32le -s W'xH' -r 20 -i PATH); the
+ *     geometry goes to stderr.  Frames come down asynchronously into two pinned buffers: frame k - 1 is written while frame k computes
+ *     and copies.
  * Output: the final `sum` image; on stderr the number of frames and max|sum - input| (0 up to rounding when the method visits
- * every pixel exactly once and the whole scan is run).
+ * every pixel exactly once and the whole scan is run).  Without the frame options the output is what it was before they existed.
  */
 #include <math.h>
 #include <stdint.h>
@@ -38,7 +45,37 @@
 #define HIP(x) do { if ((x) != hipSuccess) { fprintf(stderr, "HIP error at %s:%d\n", __FILE__, __LINE__); return 1; } } while (0)
 #define DSP(x) do { if (x) { fprintf(stderr, "dspfft: %s (%s:%d)\n", dspfft_last_error(), __FILE__, __LINE__); return 1; } } while (0)
 
-#define FILL_ID 0xFFFFFFFEu           /* the id the fill's pixels are stamped with (frame ids stay below limit + nframes) */
+#define FILL_ID 0xFFFFFFFEu
+
+/* speclib.c:42-77 spec_params_parse over k=v pairs separated by ':' (scale=, sign=, preset= or a preset's name as a key); returns the
+ * pair that failed to parse, or NULL */
+static const char *parse_spec_opts(const char *opts, int *scale, int *sign)
+{
+	static const char *scales[] = {"linear", "log"}, *signs[] = {"abs", "shift", "saturate"};
+	static const struct { const char *name; int scale, sign; } presets[] = {{"abs", 2, 1}, {"shift", 2, 2}, {"flat", 1, 2}, {"signmap", 1, 3}};
+	const char *p = opts;
+	while (*p) {
+		const char *end = strchr(p, ':');
+		size_t len = end ? (size_t)(end - p) : strlen(p);
+		char kv[64];
+		if (len >= sizeof kv) return p;
+		memcpy(kv, p, len); kv[len] = 0;
+		if (len) {
+			char *val = strchr(kv, '=');
+			if (val) *val++ = 0; else val = kv + len;
+			int ok = 0;
+			if (!strcmp(kv, "scale")) { for (int i = 0; i < 2; i++) if (!strcmp(val, scales[i])) { *scale = i + 1; ok = 1; } }
+			else if (!strcmp(kv, "sign")) { for (int i = 0; i < 3; i++) if (!strcmp(val, signs[i])) { *sign = i + 1; ok = 1; } }
+			else {
+				const char *key = strcmp(kv, "preset") ? kv : val;
+				for (int i = 0; i < 4; i++) if (!strcmp(key, presets[i].name)) { *scale = presets[i].scale; *sign = presets[i].sign; ok = 1; }
+			}
+			if (!ok) return p;
+		}
+		p += len + (end != NULL);
+	}
+	return NULL;
+}           /* the id the fill's pixels are stamped with (frame ids stay below limit + nframes) */
 
 int main(int argc, char *argv[])
 {
@@ -46,9 +83,26 @@ int main(int argc, char *argv[])
 	const char *pos[4] = {NULL, NULL, NULL, NULL};
 	int npos = 0, skip = 0, invert = 0;
 	size_t offset = 0, nframes = 0;
+	dspfft_scan_frame_opts fo;
+	memset(&fo, 0, sizeof fo);
+	int parity = 0;
+	const char *video = NULL;
 	for (int a = 1; a < argc; a++) {
 		const char *s = argv[a];
-		if ((!strcmp(s, "--offset") || !strcmp(s, "-O") || !strcmp(s, "--frames") || !strcmp(s, "-n")) && a + 1 < argc) {
+		if (!strcmp(s, "-v") || !strcmp(s, "--visualize")) fo.visualize = 1;
+		else if (!strcmp(s, "-s") || !strcmp(s, "--spectrogram")) fo.spectrogram = fo.visualize = 1;
+		else if (!strcmp(s, "-i") || !strcmp(s, "--intermediates")) fo.intermediates = 1;
+		else if (!strcmp(s, "-M") || !strcmp(s, "--max-intermediates")) fo.intermediates = fo.max_intermediates = 1;
+		else if (!strcmp(s, "-P") || !strcmp(s, "--measure-parity")) parity = 1;
+		else if (!strcmp(s, "-g") || !strcmp(s, "--linear")) {
+			fprintf(stderr, "--linear is not supported: it needs ImageMagick's colourspace transform and libavutil's transfer function\n");
+			return 2;
+		} else if (!strcmp(s, "--spec-gain") && a + 1 < argc) fo.spec_gain = strtod(argv[++a], NULL);        /* precision_strtoi, INTERMEDIATE=D */
+		else if (!strcmp(s, "--spec-opts") && a + 1 < argc) {
+			const char *e = parse_spec_opts(argv[++a], &fo.spec_scaletype, &fo.spec_signtype);
+			if (e) { fprintf(stderr, "Couldn't parse spec option starting at: %s\n", e); return 2; }
+		} else if (!strcmp(s, "--video") && a + 1 < argc) video = argv[++a];
+		else if ((!strcmp(s, "--offset") || !strcmp(s, "-O") || !strcmp(s, "--frames") || !strcmp(s, "-n")) && a + 1 < argc) {
 			const size_t v = strtoul(argv[++a], NULL, 10);
 			if (s[1] == 'O' || s[2] == 'o') offset = v; else nframes = v;
 		} else if (!strcmp(s, "--skip")) skip = 1;
@@ -57,11 +111,16 @@ int main(int argc, char *argv[])
 		else if (npos < 4) pos[npos++] = s;
 		else { fprintf(stderr, "too many arguments\n"); return 2; }
 	}
-	if (npos < 2) { fprintf(stderr, "usage: %s <in> <out.pf> [step] [method] [--offset N] [--skip] [--invert] [--frames N]\n", argv[0]); return 2; }
+	if (npos < 2) {
+		fprintf(stderr, "usage: %s <in> <out.pf> [step] [method] [--offset N] [--skip] [--invert] [--frames N] [-v] [-s] [--spec-gain G] "
+		        "[--spec-opts k=v:...] [-i] [-M] [-P] [--video PATH]\n", argv[0]);
+		return 2;
+	}
 	size_t width, height;
 	const int channels = 3;
 	float *pix;
 	if (read_image(pos[0], &width, &height, &pix)) { fprintf(stderr, "cannot read %s\n", pos[0]); return 1; }
+	const int frames_on = fo.visualize || fo.intermediates || parity || video != NULL;
 	const char *mname = npos > 3 ? pos[3] : "zigzag";
 	const uint32_t w = (uint32_t)width, h = (uint32_t)height;
 	const size_t npix = width * height, n = npix * channels;
@@ -127,6 +186,43 @@ int main(int argc, char *argv[])
 	if (!nframes || nframes > limit / step) nframes = (limit + step - 1) / step;                  /* scan.c:347-348 */
 	if (offset >= limit) offset = limit - 1;                                                      /* scan.c:385-386 */
 	const int fill = !skip && offset > 0;
+	/* ---- the output frames (scan.c:366-536) ---- */
+	dspfft_scanframes sf = NULL;
+	float *d_frame = NULL, *d_image = NULL, *d_orig = NULL, *h_frame[2] = {NULL, NULL};
+	uint32_t *d_mark = NULL;                /* owner index with DC keeping its index (the marks); NULL: coordinate lists */
+	FILE *vf = NULL;
+	size_t ffloats = 0;
+	hipEvent_t ev[2];
+	if (frames_on) {
+		FILE *f = fopen(pos[0], "rb");
+		char magic[3] = {0, 0, 0};
+		if (!f || fread(magic, 1, 2, f) != 2) { fprintf(stderr, "cannot read %s\n", pos[0]); return 1; }
+		fclose(f);
+		fo.parity_depth = parity ? (!strcmp(magic, "P6") ? 8 : 32) : 0;                           /* host/rawio.h: P6 8-bit, PF float */
+		DSP(dspfft_scanframes_create(&sf, w, h, &fo));
+		ffloats = dspfft_scanframes_frame_floats(sf);
+		HIP(hipMalloc((void **)&d_frame, ffloats * 4));
+		if (fo.intermediates) {
+			HIP(hipMalloc((void **)&d_image, n * 4));
+			HIP(hipMemsetD32((hipDeviceptr_t)d_image, 0x80000000u, n));                           /* -0.0f: the step adds into it */
+		}
+		if (parity) {
+			HIP(hipMalloc((void **)&d_orig, n * 4));
+			HIP(hipMemcpy(d_orig, pix, n * 4, hipMemcpyHostToDevice));
+		}
+		if (fo.visualize && !per_frame_lists) {
+			HIP(hipMalloc((void **)&d_mark, npix * 4));
+			if (method >= 0) DSP(dspfft_scan_owner_index(d_mark, method, w, h, NULL));
+			else HIP(hipMemcpy(d_mark, d_ids, npix * 4, hipMemcpyDeviceToDevice));
+		}
+		if (video) {
+			if (!(vf = fopen(video, "wb"))) { fprintf(stderr, "cannot write %s\n", video); return 1; }
+			for (int k = 0; k < 2; k++) { HIP(hipHostMalloc((void **)&h_frame[k], ffloats * 4, 0)); HIP(hipEventCreate(&ev[k])); }
+			fprintf(stderr, "video: %zu frames of gbrpf32le %zux%zu (ffmpeg -f rawvideo -pix_fmt gbrpf32le -s %zux%zu -r 20 -i %s)\n", nframes,
+			        width * (1 + fo.visualize), height * (1 + fo.intermediates), width * (1 + fo.visualize), height * (1 + fo.intermediates), video);
+		}
+		DSP(dspfft_scanframes_begin(sf, d_frame, d_coeffs, NULL));
+	}
 	if (!per_frame_lists && (fill || invert)) {                                                   /* the owner index, DC unmarked */
 		HIP(hipMalloc((void **)&d_index, npix * 4));
 		if (method >= 0) DSP(dspfft_scan_owner_index(d_index, method, w, h, NULL));
@@ -155,10 +251,12 @@ int main(int argc, char *argv[])
 				HIP(hipMemcpy(d_lin, h_lin, cnt * 4, hipMemcpyHostToDevice)); \
 			} \
 			DSP(dspfft_scan_stamp(d_ids, d_lin, cnt, (id), NULL)); \
+			if (sf) DSP(dspfft_scanframes_mark_coords(sf, d_frame, d_coeffs, d_lin, cnt, (id) != FILL_ID, NULL)); \
 		} \
 	} while (0)
 	if (fill) {                                                                                   /* scan.c:389-417 */
 		const size_t a = invert ? limit - offset : 0, b = invert ? limit : offset;
+		if (d_mark) DSP(dspfft_scanframes_mark_range(sf, d_frame, d_coeffs, d_mark, (uint32_t)a, (uint32_t)b, 0, NULL));
 		if (per_frame_lists) {
 			STAMP(a, b, FILL_ID);
 			DSP(dspfft_execute_masked_accumulate(inv, d_coeffs, d_work, d_sum, d_ids, FILL_ID, channels, NULL));
@@ -166,12 +264,43 @@ int main(int argc, char *argv[])
 	}
 	for (size_t i = offset; i < offset + nframes; i++) {                                          /* scan.c:421-459 */
 		const size_t lo = i * step, hi = lo + step < limit ? lo + step : limit;
-		if (lo >= limit) continue;                       /* no scan index left: the frame adds nothing (the sum is emitted unchanged) */
-		const size_t a = invert ? limit - hi : lo, b = invert ? limit - lo : hi;                 /* scan.c:424 j = limit - 1 - s */
-		if (per_frame_lists) STAMP(a, b, (uint32_t)i);
-		if (invert && !per_frame_lists)
-			DSP(dspfft_execute_masked_accumulate_range(inv, d_coeffs, d_work, d_sum, d_index, (uint32_t)a, (uint32_t)b, channels, NULL));
-		else DSP(dspfft_execute_masked_accumulate(inv, d_coeffs, d_work, d_sum, d_ids, (uint32_t)i, channels, NULL));
+		float *acc = d_image ? d_image : d_sum;          /* -i: this frame's inverse alone, added to the sum by compose */
+		if (lo < limit) {
+			const size_t a = invert ? limit - hi : lo, b = invert ? limit - lo : hi;             /* scan.c:424 j = limit - 1 - s */
+			if (d_mark) DSP(dspfft_scanframes_mark_range(sf, d_frame, d_coeffs, d_mark, (uint32_t)a, (uint32_t)b, 1, NULL));
+			if (per_frame_lists) STAMP(a, b, (uint32_t)i);
+			if (invert && !per_frame_lists)
+				DSP(dspfft_execute_masked_accumulate_range(inv, d_coeffs, d_work, acc, d_index, (uint32_t)a, (uint32_t)b, channels, NULL));
+			else DSP(dspfft_execute_masked_accumulate(inv, d_coeffs, d_work, acc, d_ids, (uint32_t)i, channels, NULL));
+		} else if (!sf) continue;                        /* no scan index left: the frame adds nothing (the sum is emitted unchanged) */
+		else if (d_mark) DSP(dspfft_scanframes_mark_range(sf, d_frame, d_coeffs, d_mark, 0, 0, 1, NULL));     /* clears the last marks */
+		else if (fo.visualize) DSP(dspfft_scanframes_mark_coords(sf, d_frame, d_coeffs, NULL, 0, 1, NULL));
+		if (!sf) continue;
+		DSP(dspfft_scanframes_compose(sf, d_frame, d_sum, d_image, d_coeffs, d_orig, i - offset, NULL));
+		if (vf) {
+			const size_t k = (i - offset) & 1;
+			HIP(hipMemcpyAsync(h_frame[k], d_frame, ffloats * 4, hipMemcpyDeviceToHost, NULL));
+			HIP(hipEventRecord(ev[k], NULL));
+			if (i > offset) {                            /* the previous frame is written while this one copies */
+				HIP(hipEventSynchronize(ev[k ^ 1]));
+				if (fwrite(h_frame[k ^ 1], 4, ffloats, vf) != ffloats) { fprintf(stderr, "error writing %s\n", video); return 1; }
+			}
+		}
+	}
+	if (vf) {
+		if (nframes) {
+			const size_t k = (nframes - 1) & 1;
+			HIP(hipEventSynchronize(ev[k]));
+			if (fwrite(h_frame[k], 4, ffloats, vf) != ffloats) { fprintf(stderr, "error writing %s\n", video); return 1; }
+		}
+		if (fclose(vf)) { fprintf(stderr, "error writing %s\n", video); return 1; }
+		for (int k = 0; k < 2; k++) { HIP(hipHostFree(h_frame[k])); HIP(hipEventDestroy(ev[k])); }
+	}
+	if (parity) {                                                                                 /* scan.c:530-536 */
+		uint64_t pf;
+		DSP(dspfft_scanframes_parity(sf, &pf, NULL));
+		if (pf == UINT64_MAX) fprintf(stderr, "Didn't reach parity with the original image before the end of the scan.\n");
+		else fprintf(stderr, "Reached parity with the original image at scan index %llu\n", (unsigned long long)pf);
 	}
 	#undef STAMP
 	float *sum = malloc(n * 4);
@@ -181,7 +310,9 @@ int main(int argc, char *argv[])
 	fprintf(stderr, "method %s: %zu scan indices, %zu frames of %zu, device-resident; max|sum-input| = %.3e\n", mname, (size_t)limit, nframes, step, err);
 	const int rc = write_pf(pos[1], width, height, sum);
 	dspfft_destroy_plan(fwd); dspfft_destroy_plan(inv);
+	dspfft_scanframes_destroy(sf);
 	hipFree(d_coeffs); hipFree(d_sum); hipFree(d_work); hipFree(d_ids); hipFree(d_index); hipFree(d_lin);
+	hipFree(d_frame); hipFree(d_image); hipFree(d_orig); hipFree(d_mark);
 	free(sum); free(pix); free(h_lin); scan_order_list_free(&fl);
 	return rc;
 }

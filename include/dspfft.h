@@ -351,6 +351,58 @@ size_t dspfft_scan_magnitude_work_bytes(uint32_t w, uint32_t h);
 int dspfft_scan_magnitude_index(uint32_t *d_index, const float *d_coeffs, uint32_t w, uint32_t h, int channels, double qfactor,
                                 void *d_work, size_t work_bytes, uint32_t *limit, void *hip_stream);
 
+/* ---- scan's output frames on the device (scan/scan.c:366-375,379-417,419-536), HIP-only entry points ----
+ * The frame scan hands its encoder each output step: AV_PIX_FMT_GBRPF32LE, three planes of W' = w (1 + visualize) by H' = h (1 + intermediates)
+ * floats in plane order G, B, R (channel z = 0, R, is plane 2; z = 1 plane 0; z = 2 plane 1), dspfft_scanframes_frame_floats floats in all.
+ * Panels: top-left the reconstruction `sum`; top-right (-v) every visited coefficient, 1.0 or with -s its spectrogram value
+ * sign(scale(c * spec_normalization_2d(x, y) * gain) / max) in double (speclib.c:133-174; gain and the DC pixel's largest channel rounded to
+ * float first, as spec_create's `coeff` arguments round them); bottom-left (-i) this frame's inverse plus DC, ((image + dc) - min) / (max - min)
+ * in float with min, max = 0, 1 or (-M) the frame's per-channel min / max plus DC (an all-zero image gives NaN under -M, as the reference
+ * writes); bottom-right (-v -i) this frame's coefficients alone.  Panels the reference never clears keep their contents between frames.
+ * Per run: begin (clears the frame, as ffapi_clear_frame, and sets the scaler from the DC pixel of d_coeffs), mark the fill's indices
+ * (current = 0), then per frame: mark the frame's indices (current = 1), the fused step, compose.
+ * With -i the fused step must add into an IMAGE buffer of w h 3 floats holding -0.0f (0x80000000) instead of d_sum: -0 + v == v, so the
+ * buffer receives exactly what the fused store would have added to the sum; compose then adds it to d_sum (the same float as the fused
+ * path) and refills it with -0.0f for the next frame.  The caller fills it with -0.0f once.  All buffers interleave channels (HWC).
+ * Stream-ordered, no host synchronisation except dspfft_scanframes_parity.  Frame offsets are 64-bit. */
+typedef struct {
+	int visualize;                          /* -v: the right-hand panels */
+	int spectrogram;                        /* -s (implies -v): spectrogram values instead of 1.0 */
+	int intermediates;                      /* -i: the bottom panels */
+	int max_intermediates;                  /* -M (implies -i): the bottom-left panel normalised by its own min / max */
+	double spec_gain;                       /* --spec-gain; 0: 127.5 sqrt(4 w h) (scan.c:367-368) */
+	int spec_scaletype;                     /* speclib's scaletype: 0 none (= log), 1 linear, 2 log */
+	int spec_signtype;                      /* speclib's signtype: 0 none (= abs), 1 abs, 2 shift, 3 saturate */
+	int parity_depth;                       /* -P: 0 off; the original's bit depth, 1..16 (lroundf of value * (2^depth - 1)) or 32 (float ==) */
+} dspfft_scan_frame_opts;
+typedef struct dspfft_scanframes_s *dspfft_scanframes;
+/* -s implies -v and -M implies -i, as scan.c:179-186 sets them.  A build without the kernels (the CPU emulation) creates the handle and
+ * answers frame_floats; every call that launches reports "not in this build". */
+int dspfft_scanframes_create(dspfft_scanframes *sf, uint32_t w, uint32_t h, const dspfft_scan_frame_opts *opts);
+/* 3 W' H' */
+size_t dspfft_scanframes_frame_floats(dspfft_scanframes sf);
+/* clears d_frame, sets the scaler from d_coeffs[0..2] and resets the parity measurement */
+int dspfft_scanframes_begin(dspfft_scanframes sf, float *d_frame, const float *d_coeffs, void *hip_stream);
+/* lights the top-right panel at every pixel whose owner scan index lies in [lo, hi) (d_owner: an owner-index table in which DC KEEPS its
+ * index -- dspfft_scan_owner_index, or a magnitude / file index -- not the fused step's tables, where DC is 0xFFFFFFFF).  current != 0 (the
+ * frame being emitted; with -i): the bottom-right panel is first cleared where the previous current call lit it, then lit alike.
+ * lo == hi lights nothing (a frame past the scan's limit) but still clears.  No-op without -v. */
+int dspfft_scanframes_mark_range(dspfft_scanframes sf, float *d_frame, const float *d_coeffs, const uint32_t *d_owner, uint32_t lo, uint32_t hi,
+                                 int current, void *hip_stream);
+/* the same from y*w+x lists (dspfft_scan_coords layout; 0xFFFFFFFF slots skipped): box, and `file` orders whose indices share pixels.
+ * With current != 0 the list is copied (the next current call clears the bottom-right panel there). */
+int dspfft_scanframes_mark_coords(dspfft_scanframes sf, float *d_frame, const float *d_coeffs, const uint32_t *d_lin, uint64_t nslots,
+                                  int current, void *hip_stream);
+/* one launch per frame (plus -M's two-pass min / max and -P's one-lane flag update): d_sum += d_image when d_image is given (required with
+ * -i; NULL without it: the fused step added into d_sum), the top-left and bottom-left panels, d_image back to -0.0f.  -P: compares
+ * d_sum with d_original (w h 3 floats, required with parity_depth) until the first frame at parity; `frame` (0-based, i - offset in scan's
+ * loop) is what dspfft_scanframes_parity reports. */
+int dspfft_scanframes_compose(dspfft_scanframes sf, float *d_frame, float *d_sum, float *d_image, const float *d_coeffs, const float *d_original,
+                              uint64_t frame, void *hip_stream);
+/* synchronises the stream; *first_frame = the first frame at parity, UINT64_MAX if none was */
+int dspfft_scanframes_parity(dspfft_scanframes sf, uint64_t *first_frame, void *hip_stream);
+void dspfft_scanframes_destroy(dspfft_scanframes sf);
+
 /* ---- the rest of motion's block loop (motion/motion.c), HIP-only entry points ---- */
 enum { DSPFFT_MOTION_NONE = 0, DSPFFT_MOTION_ABS = 1, DSPFFT_MOTION_SHIFT = 2, DSPFFT_MOTION_FLAT = 3, DSPFFT_MOTION_COPY = 4 };
 /* motion.c:617-640: the {n[0],n[1],n[2]} corner of an 8-bit buffer -> float, both laid out as planes of minbuf_hw[0] x minbuf_hw[1];
