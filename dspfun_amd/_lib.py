@@ -18,7 +18,7 @@ SYMBOLS = [
     "dspfft_plan_many_r2r_f64", "dspfft_plan_set_scale_f64", "dspfft_plan_set_axis_scale0_f64", "dspfft_execute_f64", "dspfft_execute_masked_accumulate_f64", "dspfft_plan_scan_prepare", "dspfft_plan_set_input_window", "dspfft_plan_set_output_alternate", "dspfft_set_plan_effort", "dspfft_get_plan_effort",
     "dspfft_plan_many_r2r_ordered", "dspfft_plan_guru_r2r", "dspfft_execute_roundtrip", "dspfft_execute_roundtrip_u8", "dspfft_execute_roundtrip_u8_dither",
     "dspfft_execute", "dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
-    "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
+    "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_execute_n", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
     "dspfft_last_error", "dspfft_version", "dspfft_set_thread_plan_effort", "dspfft_get_thread_plan_effort", "dspfft_fftw_sparse_uploads",
     "dspfft_scan_zigzag", "dspfft_scan_zigzag_frame_ids", "dspfft_execute_masked_accumulate", "dspfft_execute_masked_accumulate_range", "dspfft_execute_masked_accumulate_range_f64", "dspfft_scan_scatter", "dspfft_accumulate", "dspfft_broadcast_dc",
     "dspfft_scan_limit", "dspfft_scan_max_interval", "dspfft_scan_coord_slots", "dspfft_scan_owner_index", "dspfft_scan_frame_ids", "dspfft_scan_coords", "dspfft_scan_stamp",
@@ -26,6 +26,7 @@ SYMBOLS = [
     "dspfft_u8_to_f32", "dspfft_f32_to_u8",
     "dspfft_zoom_ncomponents", "dspfft_zoom_basis", "dspfft_zoom_work_floats", "dspfft_zoom_product", "dspfft_gemm_nt_f32",
     "dspfft_zoom_last_error", "dspfft_zoomfft_create", "dspfft_zoomfft_work_floats", "dspfft_zoomfft_execute", "dspfft_zoomfft_destroy", "dspfft_zoomfft_last_error", "dspfft_zoomczt_create", "dspfft_zoomczt_work_floats", "dspfft_zoomczt_execute", "dspfft_zoomczt_destroy",
+    "dspfft_zoomanim_create", "dspfft_zoomanim_work_floats", "dspfft_zoomanim_set_coeffs", "dspfft_zoomanim_execute", "dspfft_zoomanim_destroy", "dspfft_zoomanim_last_error",
     "dspfft_scanframes_create", "dspfft_scanframes_frame_floats", "dspfft_scanframes_begin", "dspfft_scanframes_mark_range", "dspfft_scanframes_mark_coords",
     "dspfft_scanframes_compose", "dspfft_scanframes_parity", "dspfft_scanframes_destroy",
     "dspfft_applybasis_work_floats", "dspfft_applybasis_partsums",
@@ -76,6 +77,15 @@ def bind(lib):
     lib.dspfft_cosrows_destroy.restype = None
     lib.dspfft_cztrows_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int]
     lib.dspfft_cztrows_execute.argtypes = [vp, vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_longlong, C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double, vp]
+    lib.dspfft_cztrows_execute_n.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_longlong, C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double, vp]
+    lib.dspfft_zoomanim_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.dspfft_zoomanim_work_floats.restype = C.c_size_t
+    lib.dspfft_zoomanim_work_floats.argtypes = [vp]
+    lib.dspfft_zoomanim_set_coeffs.argtypes = [vp, vp, vp]
+    lib.dspfft_zoomanim_execute.argtypes = [vp] + [C.c_double] * 6 + [C.c_int, C.c_int, vp, vp, vp]
+    lib.dspfft_zoomanim_destroy.argtypes = [vp]
+    lib.dspfft_zoomanim_destroy.restype = None
+    lib.dspfft_zoomanim_last_error.restype = C.c_char_p
     lib.dspfft_cztrows_length.argtypes = [vp]
     lib.dspfft_cztrows_destroy.argtypes = [vp]
     lib.dspfft_cztrows_destroy.restype = None

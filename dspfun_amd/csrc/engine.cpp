@@ -23,6 +23,7 @@
 #include "../../include/dspfft.h"
 #include "backend.h"
 #include "scan_frame_core.h"
+#include "zoom_anim_core.h"
 
 using namespace dspfft;
 
@@ -33,6 +34,9 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_launch(
 
 // scan_frame.hip's launcher (the dspfft_scanframes_* bodies).  Weak, as dspfft_dither_launch: the CPU emulation build reports "not in this build".
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_scanframes_launch(dspfft::SfOp *o, char *err, size_t errlen);
+// zoom_anim.hip's launcher (the overlay and planar store of dspfft_zoomanim_execute).  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_zoomanim_finish_launch(float *d_out, const float *src, const dspfft::ZaOverlay *o,
+                                                                                          int planar, void *stream, char *err, size_t errlen);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -1477,12 +1481,16 @@ extern "C" int dspfft_cztrows_create(dspfft_cztrows *out, int nc, int nout, int 
 	return 0;
 }
 extern "C" int dspfft_cztrows_length(dspfft_cztrows p) { return p ? p->P : 0; }
-extern "C" int dspfft_cztrows_execute(dspfft_cztrows p, const float *d_in, long long in_group, long long in_pitch, int es_in,
-                                      float *d_out, long long out_group, long long out_pitch, int es_out, double omega, double phi, double scale, void *stream)
+extern "C" int dspfft_cztrows_execute_n(dspfft_cztrows p, int nc, int lines, const float *d_in, long long in_group, long long in_pitch, int es_in,
+                                        float *d_out, long long out_group, long long out_pitch, int es_out, double omega, double phi, double scale, void *stream)
 {
 	if (!p || !d_in || !d_out || es_in < 1 || es_out < 1) return fail(-1, "null plan or buffer, or a stride below 1");
+	if (nc < 1 || nc > p->nc || lines < 1 || lines > p->lines || lines % p->group)
+		return fail(-1, "extents (nc %d, lines %d) outside the plan's (nc %d, lines %d, group %d)", nc, lines, p->nc, p->lines, p->group);
 	if (3u & ((uintptr_t)d_in | (uintptr_t)d_out)) return fail(-1, "buffers must be 4-byte aligned");
 	const bool fresh = !(omega == p->omega_of_spectrum);
+	// the tables always for the plan's nc: the chirp's spectrum then serves every nc <= p->nc (a line of nc' components convolves with
+	// h[m], m in (-(nc' - 1), nout), a sub-range of what it holds, and P >= p->nc + nout - 1 >= nc' + nout - 1); f0 reads only n < nc
 	if (int rc = be_czt_tables(p->atab, p->etab, fresh ? p->htab : nullptr, p->nc, p->nout, p->P, omega, phi, scale, stream)) return fail(-4, "table kernel launch failed: backend code %d", rc);
 	CztArgs a;
 	a.in = nullptr; a.out = nullptr; a.atab = p->htab; a.hspec = nullptr; a.etab = nullptr; a.W = (const cf *)p->W;
@@ -1493,9 +1501,15 @@ extern "C" int dspfft_cztrows_execute(dspfft_cztrows p, const float *d_in, long 
 	}
 	a.in = d_in; a.out = d_out; a.atab = p->atab; a.hspec = p->hspec; a.etab = p->etab;
 	a.in_pitch = in_pitch; a.out_pitch = out_pitch; a.in_group = in_group; a.out_group = out_group; a.es_in = es_in; a.es_out = es_out;
-	a.nc = p->nc; a.nout = p->nout; a.lines = p->lines; a.group = p->group;
+	a.nc = nc; a.nout = p->nout; a.lines = lines; a.group = p->group;
 	if (int rc = be_launch_czt_rows(p->id, a, stream)) return fail(-4, "kernel launch failed (chirp-z rows, P = %d): backend code %d", p->P, rc);
 	return 0;
+}
+extern "C" int dspfft_cztrows_execute(dspfft_cztrows p, const float *d_in, long long in_group, long long in_pitch, int es_in,
+                                      float *d_out, long long out_group, long long out_pitch, int es_out, double omega, double phi, double scale, void *stream)
+{
+	if (!p) return fail(-1, "null plan or buffer, or a stride below 1");
+	return dspfft_cztrows_execute_n(p, p->nc, p->lines, d_in, in_group, in_pitch, es_in, d_out, out_group, out_pitch, es_out, omega, phi, scale, stream);
 }
 extern "C" void dspfft_cztrows_destroy(dspfft_cztrows p)
 {
@@ -1508,6 +1522,94 @@ extern "C" int dspfft_transpose_f32(float *d_out, long long out_pitch, const flo
 	if (!d_out || !d_in || rows < 1 || cols < 1 || out_pitch < rows || in_pitch < cols) return fail(-1, "bad arguments");
 	if (int rc = be_transpose(d_out, out_pitch, d_in, in_pitch, rows, cols, stream)) return fail(-4, "kernel launch failed (transpose): backend code %d", rc);
 	return 0;
+}
+
+// ---- zoom's animation loop (include/dspfft.h dspfft_zoomanim_*; zoom/zoom.c:320-410) ----
+// dspfft_zoomczt_execute's stages (y chirp-z on the transposed coefficients, transpose, x chirp-z), with the plans sized once for the
+// largest extents a frame can need (nc = w, h; y lines w 3) and each frame running on its own (cw, ch) <= (w, h).  The coefficients are
+// transposed once (set_coeffs); a frame reads the first cw 3 lines and the first ch entries of each.
+struct dspfft_zoomanim_s {
+	int w, h, type, vw, vh;
+	bool coeffs_set;
+	float *Ct;                       // the coefficient block transposed: Ct[(u, c)][v], w 3 lines of h
+	dspfft_cztrows rows_y, rows_x;
+};
+namespace {
+size_t za_r4(size_t n) { return (n + 3) & ~(size_t)3; }
+}  // namespace
+extern "C" const char *dspfft_zoomanim_last_error(void) { return g_err; }
+extern "C" int dspfft_zoomanim_create(dspfft_zoomanim *out, int w, int h, int type, int vw, int vh)
+{
+	if (!out) return fail(-1, "null object pointer");
+	*out = nullptr;
+	if (w < 1 || h < 1 || vw < 1 || vh < 1 || type < 0 || type > 2) return fail(-1, "bad arguments (%dx%d, type %d, view %dx%d)", w, h, type, vw, vh);
+	const long long big = vh > h ? vh : h;
+	if ((long long)w * 3 * big >= (1ll << 31) || (long long)vw * vh * 3 >= (1ll << 31)) return fail(-2, "frame too large for 31-bit strides");
+	dspfft_zoomanim z = new dspfft_zoomanim_s();
+	z->w = w; z->h = h; z->type = type; z->vw = vw; z->vh = vh; z->coeffs_set = false;
+	z->rows_y = z->rows_x = nullptr;
+	z->Ct = (float *)be_alloc((size_t)w * 3 * h * sizeof(float));
+	if (!z->Ct) { delete z; return fail(-3, "no device memory for the transposed coefficients"); }
+	const int ry = dspfft_cztrows_create(&z->rows_y, h, vh, w * 3, 1);
+	const int rx = ry ? ry : dspfft_cztrows_create(&z->rows_x, w, vw, vh * 3, 3);
+	if (ry || rx) {
+		if (z->rows_y) dspfft_cztrows_destroy(z->rows_y);
+		be_free(z->Ct);
+		delete z;
+		return (ry ? ry : rx) == -2 ? -2 : -3;      // (the plan's message stays in g_err)
+	}
+	*out = z;
+	return 0;
+}
+// Yt (w 3 x vh) | T (vh x w 3) | F (vh x vw x 3: the x stage's interleaved frame when the caller asks for planes)
+extern "C" size_t dspfft_zoomanim_work_floats(dspfft_zoomanim z)
+{
+	if (!z) return 0;
+	return za_r4((size_t)z->w * 3 * z->vh) + za_r4((size_t)z->vh * z->w * 3) + za_r4((size_t)z->vh * z->vw * 3);
+}
+extern "C" int dspfft_zoomanim_set_coeffs(dspfft_zoomanim z, const float *d_coeffs, void *stream)
+{
+	if (!z || !d_coeffs) return fail(-1, "null object or buffer");
+	if (dspfft_transpose_f32(z->Ct, z->h, d_coeffs, (long long)z->w * 3, z->h, z->w * 3, stream)) return -4;
+	z->coeffs_set = true;
+	return 0;
+}
+extern "C" int dspfft_zoomanim_execute(dspfft_zoomanim z, double xnum, double xden, double ynum, double yden, double vx, double vy,
+                                       int showsamples, int layout, float *d_out, float *d_work, void *stream)
+{
+	if (!z || !d_out || !d_work) return fail(-1, "null object or buffer");
+	if (!z->coeffs_set) return fail(-1, "no coefficients: call dspfft_zoomanim_set_coeffs first");
+	if (showsamples < 0 || showsamples > 2 || layout < 0 || layout > 1) return fail(-1, "bad showsamples %d or layout %d", showsamples, layout);
+	// a finite scale at or below 1 / len (zero and negative included) is clamped to 1 / len by za_axis, as zoom.c:37-41 does
+	if (!(xden > 0) || !(yden > 0) || !std::isfinite(xnum / xden) || !std::isfinite(ynum / yden) || !std::isfinite(vx) || !std::isfinite(vy))
+		return fail(-1, "scales must be finite with positive denominators, offsets finite (the caller skips non-finite frames, zoom.c:342-345)");
+	if ((showsamples || layout == 1) && !dspfft_zoomanim_finish_launch)
+		return fail(-3, "zoom animation overlay / planar store: not in this build (the kernel is HIP-only, zoom_anim.hip)");
+	const ZaOverlay ov = za_overlay(showsamples, xnum, xden, ynum, yden, vx, vy, z->vw, z->vh);
+	const bool finish = ov.mode || layout == 1;
+	double wx, px, wy, py;
+	const int cw = za_axis(z->type, xnum, xden, z->w, vx, wx, px), ch = za_axis(z->type, ynum, yden, z->h, vy, wy, py);
+	if (!cw || !ch) return fail(-2, "centered basis: len * scale must exceed 1");
+	const long long cols = (long long)cw * 3;
+	float *Yt = d_work, *T = Yt + za_r4((size_t)z->w * 3 * z->vh), *F = T + za_r4((size_t)z->vh * z->w * 3);
+	float *X = layout == 1 ? F : d_out;
+	// y axis: ch coefficients -> vh samples on the first cw 3 columns; back to rows of cw RGB pixels; x axis into the interleaved frame
+	if (dspfft_cztrows_execute_n(z->rows_y, ch, (int)cols, z->Ct, z->h, 0, 1, Yt, z->vh, 0, 1, wy, py, 1.0, stream) ||
+	    dspfft_transpose_f32(T, cols, Yt, z->vh, (int)cols, z->vh, stream) ||
+	    dspfft_cztrows_execute_n(z->rows_x, cw, z->vh * 3, T, cols, 1, 3, X, (long long)z->vw * 3, 1, 3, wx, px, 1.0 / ((double)z->w * (double)z->h), stream))
+		return -4;
+	if (finish) {
+		char err[256] = "";
+		if (dspfft_zoomanim_finish_launch(d_out, X, &ov, layout, stream, err, sizeof err)) return fail(-4, "%s", err);
+	}
+	return 0;
+}
+extern "C" void dspfft_zoomanim_destroy(dspfft_zoomanim z)
+{
+	if (!z) return;
+	dspfft_cztrows_destroy(z->rows_y); dspfft_cztrows_destroy(z->rows_x);
+	be_free(z->Ct);
+	delete z;
 }
 
 namespace {

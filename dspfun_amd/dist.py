@@ -438,3 +438,64 @@ class FrameShardedScan:
                                                stream=self._st or 0)
         self.frame = i + 1
         return i
+
+
+class FrameShardedZoom:
+    """zoom's animation loop (zoom/zoom.c:320-410) with its frames spread over the ranks.  Frames are independent once the per-frame state
+    (zoom.resolve_frames: the table of expression values applied in zoom.c:321-345's order) is resolved; every rank resolves the whole
+    table (host-side and cheap), runs its own forward transform and renders the rendered frames shard_range deals it: no collective.
+    With K frames kept on G ranks a rank renders at most ceil(K / G), so the ceiling of the speed-up is K / ceil(K / G) (4.0x for 240
+    frames on 4 GPUs, 8.0x on 8; 3.5x for 7 frames on 4).  Frames come out on their owner only, as in FrameShardedScan.
+
+    Every frame is chirp-z (dspfft_zoomanim_*); a geometry the chirp-z plans do not cover raises (Zoom.animation keeps the dense product)."""
+
+    def __init__(self, image_hwc, vw, vh, table, present, basis_type=0, vx=0.0, vy=0.0, xscale=(1.0, 1.0), yscale=(1.0, 1.0),
+                 showsamples=0, layout="rgb", group=None, lib=None):
+        import ctypes as C
+        from . import _lib
+        from .zoom import resolve_frames, LAYOUTS
+        self.lib = lib or _lib.load()
+        self.G = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self.h, self.w, c = image_hwc.shape
+        assert c == 3 and image_hwc.dtype == torch.float32
+        self.vw, self.vh, self.showsamples, self.layout = vw, vh, showsamples, LAYOUTS[layout]
+        self.frames_all = list(resolve_frames(table, present, vx, vy, xscale, yscale))
+        self.lo, self.hi = shard_range(len(self.frames_all), self.rank, self.G)
+        self._st = SlabDCT3D._stream(image_hwc) or None
+        self.coeffs = image_hwc.contiguous().clone()
+        Plan.image(self.h, self.w, 3, REDFT10, lib=lib).execute(self.coeffs.data_ptr(), stream=self._st or 0)
+        z = C.c_void_p()
+        self._check(self.lib.dspfft_zoomanim_create(C.byref(z), self.w, self.h, basis_type, vw, vh))
+        self.z = z
+        self.work = torch.empty(self.lib.dspfft_zoomanim_work_floats(z), dtype=torch.float32, device=image_hwc.device)
+        self._check(self.lib.dspfft_zoomanim_set_coeffs(z, self.coeffs.data_ptr(), self._st))
+
+    def _check(self, rc):
+        if rc:
+            raise RuntimeError(self.lib.dspfft_zoomanim_last_error().decode())
+
+    def owner(self, d):
+        """rank that renders frame d (None for a skipped frame or one outside the table)"""
+        for k, f in enumerate(self.frames_all):
+            if f[0] == d:
+                base, rem = divmod(len(self.frames_all), self.G)
+                return k // (base + 1) if k < rem * (base + 1) else rem + (k - rem * (base + 1)) // base
+        return None
+
+    def frames(self):
+        """yields (d, frame) for this rank's frames, in order: (vh, vw, 3), or (3, vh, vw) planes G, B, R"""
+        shape = (self.vh, self.vw, 3) if self.layout == 0 else (3, self.vh, self.vw)
+        for d, xs, ys, fx, fy in self.frames_all[self.lo:self.hi]:
+            out = torch.empty(shape, dtype=torch.float32, device=self.coeffs.device)
+            self._check(self.lib.dspfft_zoomanim_execute(self.z, float(xs[0]), float(xs[1]), float(ys[0]), float(ys[1]), float(fx), float(fy),
+                                                         self.showsamples, self.layout, out.data_ptr(), self.work.data_ptr(), self._st))
+            yield d, out
+
+    def __del__(self):
+        try:
+            if getattr(self, "z", None) is not None:
+                self.lib.dspfft_zoomanim_destroy(self.z)
+                self.z = None
+        except Exception:
+            pass

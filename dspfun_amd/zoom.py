@@ -1,6 +1,7 @@
 """Host-side mirror of zoom's frame computation (zoom/zoom.c:263-265 forward transform,
 :347-375 basis generation and dense separable product) over device memory."""
 import ctypes as C
+import math
 
 from . import _lib
 from .engine import Plan, DspfftError, REDFT10
@@ -115,6 +116,10 @@ class Zoom:
             raise DspfftError(self.lib.dspfft_zoom_last_error().decode())
         return b, nc
 
+    def animation(self, vw, vh, basis_type=INTERPOLATED):
+        """a ZoomAnimation over these coefficients: per-frame scale and offset without re-planning"""
+        return ZoomAnimation(self, vw, vh, basis_type)
+
     def frame(self, vw, vh, xscale=(1.0, 1.0), yscale=(1.0, 1.0), vx=0.0, vy=0.0, basis_type=INTERPOLATED, method="auto"):
         """one output frame: (vh, vw, 3) f32.  method "auto": fast transforms on the DCT-III grid (dspfft_zoomfft_*) when the scaled lengths
         are integers and the basis is interpolated or native; chirp-z transforms (dspfft_zoomczt_*) for every other scale and the centered
@@ -142,3 +147,90 @@ class Zoom:
         if rc:
             raise DspfftError(self.lib.dspfft_zoom_last_error().decode())
         return out
+
+
+LAYOUTS = {"rgb": 0, "gbr": 1}
+
+
+def resolve_frames(table, present, vx=0.0, vy=0.0, xscale=(1.0, 1.0), yscale=(1.0, 1.0)):
+    """zoom.c:320-345 with a table in place of the expressions: row d holds the values x y S X Y would give at frame d, present[i] says
+    whether that expression was given.  S sets both scales to (value, 1), X and Y then override one axis each, x and y set the offsets;
+    the state persists across frames (and across skipped ones).  Yields (d, xscale, yscale, vx, vy) for every frame the reference renders:
+    a frame with a non-finite offset or scale is skipped, as zoom.c:342-345 does.  Finite scales of zero or below are yielded: the device
+    clamps them to 1 / len as zoom.c:37-41 does (one component, the DC term alone)."""
+    xn, xd = (float(v) for v in xscale)
+    yn, yd = (float(v) for v in yscale)
+    vx, vy = float(vx), float(vy)
+    for d, row in enumerate(table):
+        x, y, s, sx, sy = (float(v) for v in row)
+        if present[2]:
+            xn = yn = s
+            xd = yd = 1.0
+        if present[3]:
+            xn, xd = sx, 1.0
+        if present[4]:
+            yn, yd = sy, 1.0
+        if present[0]:
+            vx = x
+        if present[1]:
+            vy = y
+        if not all(math.isfinite(v) for v in (vx, vy, xn / xd, yn / yd)):
+            continue
+        yield d, (xn, xd), (yn, yd), vx, vy
+
+
+class ZoomAnimation:
+    """zoom's animation loop over one Zoom's coefficients (dspfft_zoomanim_*): one object for the geometry (vw, vh, basis), any scale and
+    offset per frame, no allocation or re-planning between frames.  When the chirp-z plans do not cover the geometry (an axis longer than
+    the listed convolutions), every frame takes the dense product (Zoom.frame(method="gemm")), which has no --showsamples overlay.
+    The coefficients are transposed once, here: call refresh() after changing zoom.coeffs in place."""
+
+    def __init__(self, zoom, vw, vh, basis_type=INTERPOLATED):
+        self.zoom, self.lib, self.torch = zoom, zoom.lib, zoom.torch
+        self.vw, self.vh, self.basis_type = vw, vh, basis_type
+        z = C.c_void_p()
+        rc = self.lib.dspfft_zoomanim_create(C.byref(z), zoom.w, zoom.h, basis_type, vw, vh)
+        if rc not in (0, -2):
+            raise DspfftError(self.lib.dspfft_zoomanim_last_error().decode())
+        self.z = z if rc == 0 else None
+        if self.z is not None:
+            self.work = self.torch.empty(self.lib.dspfft_zoomanim_work_floats(self.z), dtype=self.torch.float32, device=zoom.coeffs.device)
+            self.refresh()
+
+    def refresh(self):
+        if self.z is not None and self.lib.dspfft_zoomanim_set_coeffs(self.z, self.zoom.coeffs.data_ptr(), self.torch.cuda.current_stream().cuda_stream):
+            raise DspfftError(self.lib.dspfft_zoomanim_last_error().decode())
+
+    def frame(self, xscale, yscale, vx, vy, showsamples=0, layout="rgb", out=None):
+        """one frame: (vh, vw, 3) for layout "rgb", (3, vh, vw) planes G, B, R for "gbr"; showsamples 0 none, 1 point, 2 grid"""
+        torch, lay = self.torch, LAYOUTS[layout]
+        shape = (self.vh, self.vw, 3) if lay == 0 else (3, self.vh, self.vw)
+        if self.z is None:
+            if showsamples:
+                raise DspfftError("--showsamples is not built for the dense product (the chirp-z plans do not cover this geometry)")
+            f = self.zoom.frame(self.vw, self.vh, xscale, yscale, vx, vy, self.basis_type, method="gemm")
+            f = f if lay == 0 else f.permute(2, 0, 1)[[1, 2, 0]].contiguous()
+            if out is not None:
+                out.copy_(f)
+                return out
+            return f
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.zoom.coeffs.device)
+        rc = self.lib.dspfft_zoomanim_execute(self.z, float(xscale[0]), float(xscale[1]), float(yscale[0]), float(yscale[1]), float(vx), float(vy),
+                                              showsamples, lay, out.data_ptr(), self.work.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if rc:
+            raise DspfftError(self.lib.dspfft_zoomanim_last_error().decode())
+        return out
+
+    def frames(self, table, present, vx=0.0, vy=0.0, xscale=(1.0, 1.0), yscale=(1.0, 1.0), showsamples=0, layout="rgb"):
+        """resolve_frames' frames rendered: yields (d, frame); a new tensor per frame"""
+        for d, xs, ys, fx, fy in resolve_frames(table, present, vx, vy, xscale, yscale):
+            yield d, self.frame(xs, ys, fx, fy, showsamples, layout)
+
+    def __del__(self):
+        try:
+            if getattr(self, "z", None) is not None:
+                self.lib.dspfft_zoomanim_destroy(self.z)
+                self.z = None
+        except Exception:
+            pass

@@ -151,6 +151,11 @@ typedef struct dspfft_cztrows_s *dspfft_cztrows;
 int dspfft_cztrows_create(dspfft_cztrows *plan, int nc, int nout, int lines, int group);
 int dspfft_cztrows_execute(dspfft_cztrows plan, const float *d_in, long long in_group, long long in_pitch, int es_in,
                            float *d_out, long long out_group, long long out_pitch, int es_out, double omega, double phi, double scale, void *hip_stream);
+/* The same on a sub-extent: the first `lines` lines (a multiple of the group, <= the plan's lines), each of its first nc <= the plan's nc
+ * components; samples past nc are never read (they may hold anything, NaN included).  dspfft_cztrows_execute is this call at the plan's
+ * own extents.  The chirp's spectrum is made for the plan's nc and serves every smaller one. */
+int dspfft_cztrows_execute_n(dspfft_cztrows plan, int nc, int lines, const float *d_in, long long in_group, long long in_pitch, int es_in,
+                             float *d_out, long long out_group, long long out_pitch, int es_out, double omega, double phi, double scale, void *hip_stream);
 int dspfft_cztrows_length(dspfft_cztrows plan);      /* the convolution length P the plan runs on */
 void dspfft_cztrows_destroy(dspfft_cztrows plan);
 /* out[c * out_pitch + r] = in[r * in_pitch + c], r < rows, c < cols (the re-layout between the two axes of a chirp-z zoom frame) */
@@ -504,6 +509,32 @@ int dspfft_zoomczt_create(dspfft_zoomczt *z, int w, int h, int type, double xnum
 size_t dspfft_zoomczt_work_floats(dspfft_zoomczt z);
 int dspfft_zoomczt_execute(dspfft_zoomczt z, const float *d_coeffs, double vx, double vy, float *d_out, float *d_work, void *hip_stream);
 void dspfft_zoomczt_destroy(dspfft_zoomczt z);
+/* zoom's animation loop (zoom/zoom.c:320-410): one object per geometry (w, h, basis type, vw, vh), any scale and offset per frame.
+ * create plans the chirp-z rows of dspfft_zoomczt_* once for the largest extents a frame can need (x: nc = w over vh 3 lines; y: nc = h
+ * over w 3 lines); -2 when w + vw - 1 or h + vh - 1 exceeds the longest listed convolution (19200) -- keep the dense product then.
+ * set_coeffs transposes the h x w x 3 REDFT10^2 block once into the object; call it again whenever the buffer's contents change.
+ * execute renders one frame at xscale = xnum / xden, yscale = ynum / yden, offset (vx, vy), with zoom.c:37-41's clamp and component count
+ * per axis (a frame below 1x runs on the first cw 3 lines of ch components): no device allocation, no host synchronisation, no re-planning
+ * (the chirp spectrum of an axis is rebuilt only when its omega changes).  Always chirp-z: a pan at a fixed integer scale could take
+ * dspfft_zoomfft_*, whose offset is per call too.
+ *   showsamples  0 none, 1 point, 2 grid: zoom.c:377-390 when xscale > 1 && yscale > 1 -- (0, 1, 0) at the linear index y vh + x of the
+ *                frame (vh, not vw, as the reference); with vh > vw the reference writes past its frame and indices >= vw vh are dropped
+ *                here; negative offsets (undefined there) go through long long (zoom_anim_core.h).
+ *   layout       0 interleaved RGB (vh x vw x 3), 1 GBRPF32 (three vw x vh planes G, B, R: libavutil's comp[] order).
+ * A finite scale with len num / den < 1 -- zero and negative numerators included -- is clamped to 1 / len as zoom.c:37-41 does: one
+ * component, a frame of the DC term alone (the reference itself then asks realloc for 0 bytes of basis, zoom.c:42, and may crash).
+ * Returns -2 (nothing written) for a degenerate `centered` frame (len num - den <= 0 after the clamp), -1 for a non-finite scale or
+ * offset or a denominator <= 0 (the caller skips non-finite frames, zoom.c:342-345), -3 for any showsamples != 0 or layout 1 in a build
+ * without the kernels (the CPU emulation), whether or not the overlay would apply to the frame.
+ * d_out and d_work (dspfft_zoomanim_work_floats floats) 16-byte aligned; one object serves one stream at a time. */
+typedef struct dspfft_zoomanim_s *dspfft_zoomanim;
+int dspfft_zoomanim_create(dspfft_zoomanim *z, int w, int h, int type, int vw, int vh);
+size_t dspfft_zoomanim_work_floats(dspfft_zoomanim z);
+int dspfft_zoomanim_set_coeffs(dspfft_zoomanim z, const float *d_coeffs, void *hip_stream);
+int dspfft_zoomanim_execute(dspfft_zoomanim z, double xnum, double xden, double ynum, double yden, double vx, double vy,
+                            int showsamples, int layout, float *d_out, float *d_work, void *hip_stream);
+void dspfft_zoomanim_destroy(dspfft_zoomanim z);
+const char *dspfft_zoomanim_last_error(void);
 
 /* ---- applybasis' basis x pixel partial sums on the matrix cores ----
  * applybasis/applybasis.c:410-431, forward direction:
