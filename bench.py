@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark (BASELINE.json): Mpixels/s of the DCT-II + DCT-III roundtrip on
 3840x2160x3 f32 frames, device-resident, as a fraction of the MI355X HBM roofline.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ...`, one rank per GPU)
 
 A "step" = one roundtrip (2-D REDFT10 in place, then 2-D REDFT01 in place with the 1/(4wh) gain
@@ -10,10 +10,13 @@ fused) over a batch of FRAMES independent frames per GPU -- the per-frame plan o
 spec/ispec.c:165, and what motion's default `-b 0x0x1` runs per frame (motion/motion.c:174,613-753).
 Frames are independent units, so ranks shard them with no data-path collective (weak scaling).
 
-One JSON line on stdout (rank 0).  roofline.* describes the dominant kernel, timed with HIP events on
-the launch stream (torch's current stream -- the library launches on the stream handle it is given).
-cpu_baseline is the oracle's O(N log N) CPU port (oracle/cpu_port.c, "kind": "port"), timed on the
-host cores of the same box on a bounded sample; it is a reported baseline, not the target.
+One JSON line on stdout (rank 0).  A plain run does only what the headline needs: set-up, the forward
+check, warm-up, the timed steps, the drift check and roofline.* from the events of the timed region
+(the dominant kernel, timed with HIP events on the launch stream -- the library launches on the stream
+handle it is given).  --full adds the legs that take runs of their own: single_stream_value,
+frame_latency_ms, the isolated per-kernel times, motion_c5, scan_c4, fftw_abi_end_to_end and the CPU
+baselines.  cpu_baseline is the oracle's O(N log N) CPU port (oracle/cpu_port.c, "kind": "port"),
+timed on the host cores of the same box on a bounded sample; it is a reported baseline, not the target.
 """
 import argparse
 import json
@@ -337,17 +340,22 @@ def main():
     ap.add_argument("--event-every", type=int, default=8, help="bracket the passes of one frame with events every N-th step (events between "
                     "dependent launches cost throughput: every step -3 %%, every launch -7 %%)")
     ap.add_argument("--inverse-order", choices=["columns-first", "rows-first"], default="columns-first", help="axis order of the REDFT01 plan")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single-stream", action="store_true", help="skip the single_stream_value leg (the same frames on ONE stream, after the headline)")
-    ap.add_argument("--no-fftw-abi", action="store_true", help="skip the fftw_abi_end_to_end object (one fftwf_execute on pinned host memory)")
-    ap.add_argument("--no-motion", action="store_true", help="skip the motion_c5 object (BASELINE configs[4]: per-frame blocks and the RCCL slab volume)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the legs that take runs of their own: single_stream_value, "
+                    "frame_latency_ms, roofline.isolated_*, motion_c5, scan_c4, fftw_abi_end_to_end and the CPU baselines (the --no-* options below "
+                    "leave single legs out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-single-stream", action="store_true", help="with --full: skip the single_stream_value leg (the same frames on ONE stream, after the headline)")
+    ap.add_argument("--no-fftw-abi", action="store_true", help="with --full: skip the fftw_abi_end_to_end object (one fftwf_execute on pinned host memory)")
+    ap.add_argument("--no-motion", action="store_true", help="with --full: skip the motion_c5 object (BASELINE configs[4]: per-frame blocks and the RCCL slab volume)")
     ap.add_argument("--extras-timeout", type=float, default=300.0, help="N > 1 only: seconds the motion_c5 / scan_c4 objects may take after the headline before the line is printed without them")
-    ap.add_argument("--no-scan", action="store_true", help="skip the scan_c4 object (BASELINE configs[3]: channel-sharded progressive reconstruct of an 8K frame)")
+    ap.add_argument("--no-scan", action="store_true", help="with --full: skip the scan_c4 object (BASELINE configs[3]: channel-sharded progressive reconstruct of an 8K frame)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write a fixed sample of the frames the last step returned to DIR/frames.npy "
                     "(float32, rank 0), so that two builds can be compared output for output")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:             # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_single_stream = args.no_fftw_abi = args.no_motion = args.no_scan = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # called directly as `python bench.py --gpus N`: start the N ranks ourselves, as a CHILD process of a parent
@@ -488,18 +496,20 @@ def main():
     # SURVEY 8d's timing protocol beside the batch throughput: ONE frame's forward + inverse pair alone on the chip, hipEvents around the pair on
     # the stream it is launched on, 10 pairs untimed, then 60: median and minimum (what a caller that transforms frame after frame on one
     # stream sees per frame; `value` above is four frames on two streams sharing the CUs)
-    lat = []
-    for i_ in range(70):
-        a_, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a_.record()
-        fwd.execute(ptrs[0], stream=stream); inv.execute(ptrs[0], stream=stream)
-        b_.record()
-        lat.append((a_, b_))
-    torch.cuda.synchronize()
-    lat = sorted(a_.elapsed_time(b_) for a_, b_ in lat[10:])
-    frame_latency = {"median": round(lat[len(lat) // 2], 5), "min": round(lat[0], 5), "pairs_timed": len(lat), "pairs_untimed": 10,
-                     "what": "one 3840x2160x3 frame, REDFT10^2 then REDFT01^2 in place (four launches), alone on one stream, HIP events around the pair",
-                     "Mpixels_per_s_at_median": round(H * W / lat[len(lat) // 2] / 1e3, 1)}
+    frame_latency = None
+    if args.full:
+        lat = []
+        for i_ in range(70):
+            a_, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a_.record()
+            fwd.execute(ptrs[0], stream=stream); inv.execute(ptrs[0], stream=stream)
+            b_.record()
+            lat.append((a_, b_))
+        torch.cuda.synchronize()
+        lat = sorted(a_.elapsed_time(b_) for a_, b_ in lat[10:])
+        frame_latency = {"median": round(lat[len(lat) // 2], 5), "min": round(lat[0], 5), "pairs_timed": len(lat), "pairs_untimed": 10,
+                         "what": "one 3840x2160x3 frame, REDFT10^2 then REDFT01^2 in place (four launches), alone on one stream, HIP events around the pair",
+                         "Mpixels_per_s_at_median": round(H * W / lat[len(lat) // 2] / 1e3, 1)}
     untimed_steps = max(preroll, args.warmup)
     nt = len(timed_steps) * nper
     in_region_ms = [sum(events.elapsed_ms(2 * npass * t + 2 * j, 2 * npass * t + 2 * j + 1) for t in range(nt)) / nt for j in range(npass)]
@@ -508,7 +518,8 @@ def main():
     # (single-roundtrip accuracy is what tests/test_gpu_parity.py pins: <= 5e-6)
     drift = float((frames[0] - ref0).abs().max())
     global DRIFT_BOUND
-    roundtrips_of_frame0 = untimed_steps + args.steps + (max(args.steps, 20) + max(args.warmup, 10) if single_stream_value is not None else 0) + 70
+    roundtrips_of_frame0 = (untimed_steps + args.steps + (max(args.steps, 20) + max(args.warmup, 10) if single_stream_value is not None else 0)
+                            + (70 if frame_latency is not None else 0))
     DRIFT_BOUND = max(DRIFT_BOUND, roundtrips_of_frame0 * DRIFT_PER_ROUNDTRIP)     # measured: 8.4e-7 per roundtrip
 
     # roofline object (rank 0): dominant kernel = longest average in-region launch
@@ -519,6 +530,9 @@ def main():
         for plan, tag in ((fwd, "redft10"), (inv, "redft01")):
             desc = [ln for ln in plan.describe().splitlines() if ln.startswith("axis")]
             for i in range(plan.num_passes):
+                names.append(f"{tag} {desc[i].split(':')[1].split()[0]} pass ({desc[i].strip()})")
+                if not args.full:
+                    continue
                 e2 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
                 for a, b in e2:
                     a.record()
@@ -527,8 +541,8 @@ def main():
                 torch.cuda.synchronize()
                 ms = [a.elapsed_time(b) for a, b in e2][2:]                  # first two launches warm the caches
                 iso.append(sum(ms) / len(ms))
-                names.append(f"{tag} {desc[i].split(':')[1].split()[0]} pass ({desc[i].strip()})")
-        frames[0].copy_(ref0)
+        if iso:
+            frames[0].copy_(ref0)
         k = max(range(npass), key=lambda i: in_region_ms[i])
         # algorithmic bytes of ONE launch: the 48 B/pixel roundtrip figure is 4 axis passes of 12 B/pixel each
         alg = H * W * ALG_BYTES_PER_PIXEL / 4.0
@@ -557,10 +571,11 @@ def main():
                 "all_kernels_ms": {names[i]: round(in_region_ms[i], 5) for i in range(npass)},
                 "algorithmic_bytes_per_launch": alg, "launches_timed_in_region_per_kernel": nt,
                 "note": ("durations are HIP-event averages over the timed region; with hip_streams > 1 the kernels of two frames "
-                         "share the CUs, so a launch lasts longer than when it runs alone (isolated_*)") if nstreams > 1 else
-                        "durations are HIP-event averages over the timed region",
-                "isolated_kernel_ms": {names[i]: round(iso[i], 5) for i in range(npass)},
-                "isolated_frac_dominant": round(alg / (max(iso) * 1e-3) / HBM_PEAK, 4)}
+                         "share the CUs, so a launch lasts longer than when it runs alone (isolated_*, --full)") if nstreams > 1 else
+                        "durations are HIP-event averages over the timed region"}
+        if iso:
+            roof["isolated_kernel_ms"] = {names[i]: round(iso[i], 5) for i in range(npass)}
+            roof["isolated_frac_dominant"] = round(alg / (max(iso) * 1e-3) / HBM_PEAK, 4)
 
     # BASELINE configs[4] beside the headline: motion's per-frame blocks (frame-sharded, no collective; strong and
     # weak) and its one-3-D-block mode through SlabDCT3D -- the one path that exercises RCCL all-to-all -- so that a SCALE record at
@@ -578,7 +593,7 @@ def main():
         value = pixels / 1e6 / elapsed
         line = {
             "metric": "Mpixels/s DCT-II+III roundtrip 3840x2160x3", "value": round(value, 2), "unit": "Mpixels/s",
-            "n_gpus": world, "ranks_seen_by_rccl": ranks_seen, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "ranks_seen_by_rccl": ranks_seen, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic (splitmix64 uniform [0,1), SURVEY.md 8d seed 0xD5F0002)",
             "config": {"workload": "spec + ispec roundtrip on 3840x2160 RGB float32 (BASELINE configs[1])",
@@ -595,8 +610,6 @@ def main():
             "target": {"roundtrip_frac_of_hbm_roofline": 0.70, "met": bool(value * 1e6 * ALG_BYTES_PER_PIXEL / (HBM_PEAK * world) >= 0.70),
                        "builders_model_of_this_design": {"cap": 0.366, "frac_of_it": round(value * 1e6 * ALG_BYTES_PER_PIXEL / (HBM_PEAK * world) / 0.366, 3),
                                                          "why": "two memory passes per direction are forced (no plane fits on chip); four passes at the copy floors of their access shapes = 0.366"}},
-            "single_stream_value": single_stream_value,
-            "frame_latency_ms": frame_latency,
             "forward_check": {"dc_rel_err": fwd_dc_err, "energy_rel_err": fwd_energy_err,
                               "what": "one REDFT10 x REDFT10 of frame 0 before the timed region: Y[0,0] = 4 sum(x) and sum' Y^2 = 4hw sum x^2 (a no-op fails both)"},
             "max_abs_drift_after_all_roundtrips": drift, "roundtrips_of_frame0": roundtrips_of_frame0, "host_enqueue_ms_per_step": round(enqueue_s / args.steps * 1e3, 5),
@@ -605,6 +618,9 @@ def main():
         }
         if dumped is not None:
             line["dump_outputs"] = dumped
+        if args.full:
+            line["single_stream_value"] = single_stream_value
+            line["frame_latency_ms"] = frame_latency
         if motion is not None:
             line["motion_c5"] = motion
         if scan is not None:

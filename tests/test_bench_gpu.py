@@ -1,5 +1,5 @@
-"""GPU (-m gpu): bench.py's one-line contract -- the keys the driver and the judge read, the roofline object's arithmetic, and the watchdog
-that prints the headline when the N > 1 extras do not finish."""
+"""GPU (-m gpu): bench.py's one-line contract -- the keys the driver and the judge read, the roofline object's arithmetic, what a plain run
+leaves to --full, and the watchdog that prints the headline when the N > 1 extras do not finish."""
 import json
 import os
 import subprocess
@@ -21,7 +21,8 @@ def run_bench(args, env=None, timeout=600):
 
 
 def test_one_json_line_with_the_contract_keys():
-    d = run_bench(["--gpus", "1", "--steps", "8", "--warmup", "2", "--no-motion", "--no-scan", "--no-cpu-baseline"])
+    d = run_bench(["--gpus", "1", "--steps", "8", "--warmup", "2", "--full", "--no-motion", "--no-scan", "--no-cpu-baseline"])
+    assert d["full"] is True
     assert d["metric"].startswith("Mpixels/s") and d["unit"] == "Mpixels/s" and d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 2
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32" and "synthetic" in d["data"]
     assert "workload" in d["config"] and "model" not in d["config"]
@@ -34,6 +35,7 @@ def test_one_json_line_with_the_contract_keys():
     assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / (r["kernel_ms"] * 1e-3) / 1e9) <= 2e-3 * r["achieved"]
     assert r["algorithmic_bytes_per_launch"] == 3840 * 2160 * 3 * 4
     assert r["traffic"] is None or r["traffic"] >= r["algorithmic_bytes_per_launch"]
+    assert r["isolated_kernel_ms"].keys() == r["all_kernels_ms"].keys() and 0 < r["isolated_frac_dominant"] < 1
     assert d["max_abs_drift_after_all_roundtrips"] < d["roundtrips_of_frame0"] * 2e-6 + 1e-3
     # round 4: the line says what it did
     c = d["config"]
@@ -60,10 +62,29 @@ def test_one_json_line_with_the_contract_keys():
     assert m["cap"] == 0.366 and abs(m["frac_of_it"] - d["roundtrip_frac_of_hbm_roofline"] / 0.366) < 2e-3
 
 
+def test_a_plain_run_prints_the_headline_and_leaves_the_other_legs_to_full():
+    """without --full the line carries the headline, its checks and the roofline of the timed region, and nothing that takes a run of its own"""
+    d = run_bench(["--gpus", "1", "--steps", "8", "--warmup", "2"])
+    assert d["full"] is False and d["steps"] == 8 and d["warmup"] == 2 and "error" not in d
+    assert d["metric"].startswith("Mpixels/s") and d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    frames = d["config"]["frames_per_gpu_per_step"]
+    assert abs(d["value"] - frames * 3840 * 2160 / 1e6 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    assert 20000 < d["value"] < 167000
+    assert d["config"]["untimed_steps_total"] == 700 and d["roundtrips_of_frame0"] == 700 + 8
+    assert d["forward_check"]["dc_rel_err"] < 1e-4 and d["forward_check"]["energy_rel_err"] < 1e-4
+    assert d["max_abs_drift_after_all_roundtrips"] < d["roundtrips_of_frame0"] * 2e-6 + 1e-3
+    r = d["roofline"]
+    assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / (r["kernel_ms"] * 1e-3) / 1e9) <= 2e-3 * r["achieved"]
+    assert "isolated_kernel_ms" not in r and "isolated_frac_dominant" not in r
+    for k in ("single_stream_value", "frame_latency_ms", "motion_c5", "scan_c4", "fftw_abi_end_to_end",
+              "cpu_baseline", "cpu_baseline_fftw", "cpu_baseline_scipy"):
+        assert k not in d, k
+
+
 def test_motion_volume_reports_the_exchange_fields_and_they_are_null_on_one_gpu():
     """motion_c5.volume_3d carries exchange_ms / xgmi_frac (bytes sent per rank / exchange time / 7 x 76.8 GB/s); with one rank there is
     no exchange and they are null"""
-    d = run_bench(["--gpus", "1", "--steps", "8", "--warmup", "2", "--no-scan", "--no-cpu-baseline", "--no-fftw-abi", "--no-single-stream"])
+    d = run_bench(["--gpus", "1", "--steps", "8", "--warmup", "2", "--full", "--no-scan", "--no-cpu-baseline", "--no-fftw-abi", "--no-single-stream"])
     v = d["motion_c5"]["volume_3d"]
     assert "error" not in v, v
     for k in ("exchange_ms", "xgmi_GBps_sent_per_rank", "xgmi_frac"):
@@ -73,7 +94,7 @@ def test_motion_volume_reports_the_exchange_fields_and_they_are_null_on_one_gpu(
 
 def test_watchdog_prints_the_headline_when_the_extras_do_not_finish():
     env = {"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29533", "DSPFFT_BENCH_FORCE_DIST": "1"}
-    d = run_bench(["--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--extras-timeout", "0.05"], env=env)
+    d = run_bench(["--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline", "--extras-timeout", "0.05"], env=env)
     assert d["value"] > 20000
     assert d["ranks_seen_by_rccl"] == 1                     # the RCCL path ran (one rank): an all-reduce of ones
     assert "error" in d["motion_c5"] and "not finished" in d["motion_c5"]["error"]

@@ -25,11 +25,11 @@ pmc() {     # name, command...
   rm -rf $O/${n}_FETCH_SIZE $O/${n}_WRITE_SIZE
 }
 if [ $WHAT = headline ] || [ $WHAT = all ]; then
-  python3 $R/bench.py > $O/bench.json 2> $O/bench.err || true
+  python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || true
   python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err || true
-  python3 $R/bench.py --streams 1 --no-motion --no-scan > $O/bench_streams1.json 2> $O/bench_streams1.err || true
-  trace headline python3 $R/bench.py --no-cpu-baseline --no-motion --no-scan --no-single-stream --no-fftw-abi
-  trace headline_streams1 python3 $R/bench.py --no-cpu-baseline --no-motion --no-scan --no-fftw-abi --streams 1
+  python3 $R/bench.py --full --streams 1 --no-motion --no-scan > $O/bench_streams1.json 2> $O/bench_streams1.err || true
+  trace headline python3 $R/bench.py --full --no-cpu-baseline --no-motion --no-scan --no-single-stream --no-fftw-abi
+  trace headline_streams1 python3 $R/bench.py --full --no-cpu-baseline --no-motion --no-scan --no-fftw-abi --streams 1
   cd $R; bash $R/tools/pmc_traffic.sh > $O/pmc_traffic.log 2>&1 || echo "pmc_traffic failed"; cp $R/gpurun_out/traffic.json $O/headline_traffic.json 2>/dev/null || true; cd /tmp
 fi
 if [ $WHAT = paths ] || [ $WHAT = all ]; then
