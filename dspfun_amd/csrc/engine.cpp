@@ -16,8 +16,10 @@
 #include <complex>
 #include <mutex>
 #include <dlfcn.h>
+#include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/dspfft.h"
@@ -96,9 +98,10 @@ FastDiv make_div(uint32_t d)
 
 // Tuning overrides for experiments and A/B runs (0 / unset = the built-in choice).  plan_finish() takes a snapshot of the planner switches listed
 // here (EnvScope) and everything it calls -- build_pass, build_split, build_block -- consults only that, so the passes of a plan are made under one
-// consistent set of values whatever other threads do meanwhile.  What acts OUTSIDE plan_finish reads the environment where it acts: the execute-time
-// switches (DSPFFT_LEAN01, DSPFFT_NO_FUSED_ROUNDTRIP, DSPFFT_ROW_CHAN, DSPFFT_RT_SLICE ...), dspfft_plan_scan_prepare (DSPFFT_SCAN_EIDS, DSPFFT_ZSKIP)
-// and the plan options set after creation.
+// consistent set of values whatever other threads do meanwhile.  The slice plans that a roundtrip over a clip makes later
+// (slice_plan) are made under their parent's snapshot and planning effort, which the plan keeps.  What acts OUTSIDE plan_finish reads the environment
+// where it acts.  On every call: DSPFFT_NO_FUSED_ROUNDTRIP (fused_roundtrip_off), DSPFFT_ROW_CHAN and dspfft_plan_scan_prepare's DSPFFT_SCAN_EIDS
+// and DSPFFT_ZSKIP.  Once per process, at the first use: DSPFFT_LEAN01, DSPFFT_RT_SLICE and DSPFFT_RT_STREAMS (slice_switches).
 const char *const kPlanEnv[] = {"DSPFFT_JIT", "DSPFFT_JIT_TUNE", "DSPFFT_NO_TINY", "DSPFFT_ROW_LPW", "DSPFFT_ROW_THREADS", "DSPFFT_COL_K", "DSPFFT_COL_THREADS",
                                 "DSPFFT_DENSE_STAGED", "DSPFFT_NO_SPLIT", "DSPFFT_FORCE_SPLIT", "DSPFFT_NO_BLOCK", "DSPFFT_BLOCK_G", "DSPFFT_NO_BLUESTEIN"};
 constexpr int kNPlanEnv = (int)(sizeof kPlanEnv / sizeof kPlanEnv[0]);
@@ -106,7 +109,13 @@ thread_local const int *t_plan_env = nullptr;
 struct EnvScope {
 	int v[kNPlanEnv];
 	const int *prev;
-	EnvScope() { for (int i = 0; i < kNPlanEnv; i++) { const char *e = getenv(kPlanEnv[i]); v[i] = e ? atoi(e) : 0; } prev = t_plan_env; t_plan_env = v; }
+	// the environment as it is now, or `stored` (a plan's plan_env); an enclosing scope's values hold in a scope opened inside it
+	explicit EnvScope(const int *stored = nullptr) : prev(t_plan_env)
+	{
+		if (!stored) stored = prev;
+		for (int i = 0; i < kNPlanEnv; i++) { const char *e = stored ? nullptr : getenv(kPlanEnv[i]); v[i] = stored ? stored[i] : e ? atoi(e) : 0; }
+		t_plan_env = v;
+	}
 	~EnvScope() { t_plan_env = prev; }
 };
 int env_int(const char *name)
@@ -231,10 +240,26 @@ struct dspfft_plan_s {
 	int col_kpref = 0;                       // column tile width asked of be_find_spec first (slice plans: the narrow tile, see RtSlices)
 	// dspfft_execute_roundtrip_u8 over a clip of frames: plans for a slice of the clip whose float intermediate the Infinity Cache holds
 	// (roundtrip_core), built on first use and owned by the forward plan
-	struct RtSlices { const dspfft_plan_s *inv_of = nullptr; int frames = 0; dspfft_plan_s *fwd = nullptr, *inv = nullptr, *fwd_rem = nullptr, *inv_rem = nullptr; void *side = nullptr, *ev_fork = nullptr, *ev_join = nullptr; };
-	std::vector<RtSlices> rt_slices;
+	struct RtSlices {
+		const dspfft_plan_s *inv_of = nullptr; int frames = 0;
+		dspfft_plan_s *fwd = nullptr, *inv = nullptr, *fwd_rem = nullptr, *inv_rem = nullptr;
+		void *side = nullptr, *ev_fork = nullptr, *ev_join = nullptr;
+		RtSlices() = default;
+		RtSlices(const RtSlices &) = delete;
+		RtSlices &operator=(const RtSlices &) = delete;
+		~RtSlices()
+		{
+			for (dspfft_plan_s *q : {fwd, inv, fwd_rem, inv_rem}) dspfft_destroy_plan(q);
+			if (side) be_stream_destroy(side);
+			for (void *e : {ev_fork, ev_join}) if (e) be_event_destroy(e);
+		}
+	};
+	std::vector<std::unique_ptr<RtSlices>> rt_slices;
 	std::mutex rt_mutex;                     // two host threads may run the same plan pair on their own buffers and streams: the slice plans are made once, and
 	                                         // a call's fork / slices / join are enqueued as one piece (the library stream and its two events are shared)
+	// what plan_finish made this plan under: the planning effort and the planner's switches (EnvScope); its slice plans are made under the same
+	int plan_effort = 0;
+	int plan_env[kNPlanEnv];
 };
 
 namespace {
@@ -1020,6 +1045,8 @@ const std::vector<Pass> &pick_passes(const dspfft_plan_s *pl, const void *in, co
 static int plan_finish(dspfft_plan_s *pl, dspfft_plan *plan, bool first_axis_first)
 {
 	EnvScope env;                 // the planner's switches, read once for this plan
+	pl->plan_effort = g_plan_effort;
+	memcpy(pl->plan_env, env.v, sizeof env.v);
 	size_t samples = 1;
 	pl->howmany = 1;
 	for (const Dim &b : pl->batches) { samples *= (size_t)b.n; pl->howmany *= b.n; }
@@ -1670,6 +1697,193 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
                    const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice = true,
                    const Dither *dither = nullptr);
 
+// ---- the fused roundtrip: one call, checked (rt_check), then run by one of four strategies (roundtrip_core) ----
+// DSPFFT_NO_FUSED_ROUNDTRIP=1: no fused column kernel and no slices.  Read on every call (tests toggle it inside one process).
+bool fused_roundtrip_off() { const char *e = getenv("DSPFFT_NO_FUSED_ROUNDTRIP"); return e && *e == '1'; }
+
+void motion_filter_of(const dspfft_motion_filter_params &fp, MotionFilter &mf)
+{
+	mf.ad = fp.active[0]; mf.ah = fp.active[1]; mf.aw = fp.active[2]; mf.mh = fp.minbuf_hw[0]; mf.mw = fp.minbuf_hw[1];
+	mf.b0d = fp.band_begin[0]; mf.b0h = fp.band_begin[1]; mf.b0w = fp.band_begin[2];
+	mf.b1d = fp.band_end[0]; mf.b1h = fp.band_end[1]; mf.b1w = fp.band_end[2];
+	mf.damp = fp.damp; mf.boost = fp.boost; mf.thr_lo = fp.threshold_lo; mf.thr_hi = fp.threshold_hi;
+	mf.preserve_dc = fp.preserve_dc; mf.grey_add = fp.grey_add; mf.quantizer = fp.quantizer; mf.enabled = 1;
+	motion_filter_set_divs(mf, fp.block_depth);
+}
+
+// One roundtrip call: its arguments, and what rt_check derives from them for the runners.
+// d_in8 / d_out8 non-NULL: 8-bit samples at the two ends (dspfft_execute_roundtrip_u8), d_out is then the float work buffer.
+struct RtCall {
+	dspfft_plan fwd, inv;
+	const float *d_in; float *d_out; const uint8_t *d_in8; uint8_t *d_out8; double mul8;
+	const dspfft_motion_filter_params *fp; unsigned long long *coded; void *stream;
+	// what rt_check adds (zero before)
+	const Pass *F, *I;                    // the forward plan's last pass and the inverse plan's first
+	bool rescale;                         // the inverse runs over other extents than the forward
+	bool block;                           // small blocks on aligned buffers: the fused block pass runs the call
+	bool u8_first, u8_last;               // the first forward / last inverse pass is a row pass with an 8-bit kernel of its own
+	long long span;                       // extent of the working buffer in elements
+	int nf3[3], ni3[3];                   // region geometry of the two ends (rank padded to 3 with unit extents)
+	long long sw3[3], si3[3];
+	MotionFilter mf;
+};
+
+// every rejection of a roundtrip call; nothing has been launched when it returns
+int rt_check(RtCall &c)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const dspfft_motion_filter_params *fp = c.fp;
+	if (!fwd || !inv || !(c.d_in || c.d_in8) || !c.d_out) return fail(-1, "null plan or buffer");
+	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
+	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
+	const Pass &F = *(c.F = &fwd->passes[nf - 1]), &I = *(c.I = &inv->passes[0]);
+	bool differs = fwd->rank != inv->rank;
+	for (int a = 0; !differs && a < fwd->rank; a++) differs = fwd->n[a] != inv->n[a];
+	// (plans whose blocks go through the fused block pass have no pass order to agree on)
+	if (fwd->rank != inv->rank || fwd->howmany != inv->howmany || (!differs && F.axis != I.axis && !block_roundtrip_ok(fwd, inv)))
+		return fail(-1, "the forward plan's last pass and the inverse plan's first pass must run along the same axis (create the inverse with dspfft_plan_many_r2r_ordered(..., 1))");
+	// motion's `scaled != block` (motion.c:535-552): the inverse runs over DIFFERENT extents inside the same embedding -- larger:
+	// the spectrum is zero-padded (band-limited upscale), smaller: truncated (downscale)
+	for (int a = 0; a < fwd->rank; a++) {
+		if (fwd->axes[a].os != inv->axes[a].is || inv->axes[a].is != inv->axes[a].os || fwd->kinds[a] != DSPFFT_REDFT10 || inv->kinds[a] != DSPFFT_REDFT01)
+			return fail(-1, "roundtrip: the inverse must be REDFT01, in place, on the forward (REDFT10) plan's output layout");
+		c.rescale = c.rescale || fwd->n[a] != inv->n[a];
+	}
+	if (c.rescale && (!fwd->batches.empty() || !inv->batches.empty())) return fail(-2, "roundtrip with different forward / inverse extents takes one block per call (howmany = 1)");
+	if (c.rescale)
+		for (int a = 0; a < fwd->rank; a++)
+			if (fwd->axes[a].is != fwd->axes[a].os) return fail(-2, "roundtrip with different forward / inverse extents needs ONE embedding for input, work and output (motion.c:535-552)");
+	if (fwd->batches.size() != inv->batches.size()) return fail(-1, "roundtrip: batch layouts differ");
+	for (size_t b = 0; b < fwd->batches.size(); b++)
+		if (fwd->batches[b].n != inv->batches[b].n || fwd->batches[b].os != inv->batches[b].is || inv->batches[b].is != inv->batches[b].os) return fail(-1, "roundtrip: batch layouts differ");
+	memset(&c.mf, 0, sizeof c.mf);
+	if (fp) {
+		if (fp->preserve_dc < 0 || fp->preserve_dc > 2 || fp->minbuf_hw[0] < 1 || fp->minbuf_hw[1] < 1 || fp->block_depth < 1) return fail(-1, "bad filter parameters");
+		motion_filter_of(*fp, c.mf);
+	}
+	// (the filter addresses the working buffer with 32-bit offsets)
+	c.span = 1;
+	for (int a = 0; a < fwd->rank; a++) c.span += (long long)(std::max(fwd->n[a], inv->n[a]) - 1) * fwd->axes[a].os;
+	for (const Dim &b : fwd->batches) c.span += (long long)(b.n - 1) * b.os;
+	if (fp && c.span >= (1ll << 31)) return fail(-2, "filtered roundtrip addresses the buffer with 31-bit offsets: buffer too large");
+	for (int k = 0; k < 3; k++) { c.nf3[k] = c.ni3[k] = 1; c.sw3[k] = c.si3[k] = 0; }
+	for (int a = 0; a < fwd->rank; a++) {
+		const int k = 3 - fwd->rank + a;
+		c.nf3[k] = fwd->n[a]; c.ni3[k] = inv->n[a]; c.sw3[k] = fwd->axes[a].os; c.si3[k] = fwd->axes[a].is;
+	}
+	const uintptr_t pin = c.d_in8 ? (uintptr_t)c.d_in8 : (uintptr_t)c.d_in, pout = c.d_out8 ? (uintptr_t)c.d_out8 : (uintptr_t)c.d_out;
+	c.block = !c.rescale && block_roundtrip_ok(fwd, inv) && !((c.d_in8 ? 3u : 15u) & pin) && !((c.d_out8 ? 3u : 15u) & pout);
+	c.u8_first = pass_has_u8(fwd, fwd->passes[0]);
+	c.u8_last = pass_has_u8(inv, inv->passes[ni - 1]);
+	if (c.block) return 0;
+	// the standalone filter finds a coefficient's position from its offset in a block-major embedding (minbuf_hw, block_depth); the
+	// blocks of a volume lying side by side are filtered by the fused block pass only, which knows each block's own coordinates
+	if (fp && fwd->has_block && !fwd->blk.rows_fast)
+		return fail(-2, "filtered roundtrip over the blocks of a volume needs the fused block pass: matching forward / inverse plans and 16-byte (8-bit: 4-byte) aligned buffers");
+	if (c.rescale || !(c.d_in8 || c.d_out8)) return 0;
+	// the 8-bit buffers share the plans' element layout; the unfused conversions (rt_run_passes) walk whole spans
+	if (nf < 2 || ni < 2) return fail(-2, "8-bit roundtrip needs at least two transformed axes");
+	long long ispan = 1, dense = 1;
+	for (int a = 0; a < fwd->rank; a++) { ispan += (long long)(fwd->n[a] - 1) * fwd->axes[a].is; dense *= fwd->n[a]; }
+	for (const Dim &b : fwd->batches) { ispan += (long long)(b.n - 1) * b.is; dense *= b.n; }
+	// the output conversion will be one sweep over the whole span, which must then hold nothing but samples
+	if (c.d_out8 && !c.u8_last && dense != c.span) return fail(-2, "8-bit output without a planar specialised row pass needs a dense work layout");
+	if (c.d_in8 && !c.u8_first && ispan != c.span) return fail(-2, "8-bit input without a planar specialised row pass needs identical input and work layouts");
+	return 0;
+}
+
+// small blocks: everything in one pass over the data
+int rt_run_block(const RtCall &c)
+{
+	BlockRtArgs a;
+	static_cast<BlockGeom &>(a) = c.fwd->blk;
+	const BlockGeom &o = c.inv->blk;
+	a.sy_out = o.sy_out; a.sz_out = o.sz_out; a.sxb_out = o.sxb_out;
+	for (int d = 0; d < o.nd; d++) a.bos[d] = o.bos[d];
+	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
+	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
+	a.filt = c.mf; a.coded = c.coded;
+	if (int rc = be_launch_block_roundtrip(a, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip): backend code %d", rc);
+	return 0;
+}
+
+// one block, unfused: zero the working buffer (motion.c:619), load the block region, forward, filter, inverse over the
+// scaled region, store it.  In place on a float buffer the caller has zeroed everything outside the block itself.
+int rt_run_rescale(const RtCall &c)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
+	float *const d_out = c.d_out;
+	if (c.d_in8) {
+		if (be_zero(d_out, (size_t)c.span * sizeof(float), c.stream) || be_region_u8_to_f32(d_out, c.d_in8, c.nf3, c.sw3, c.si3, c.stream)) return fail(-4, "launch failed");
+	} else if (c.d_in != d_out) {
+		if (be_zero(d_out, (size_t)c.span * sizeof(float), c.stream)) return fail(-4, "launch failed");
+	}
+	for (size_t i = 0; i < nf; i++) {
+		const Pass &P = fwd->passes[i];
+		if (int rc = run_pass<float>(fwd, P, (P.first && !c.d_in8) ? c.d_in : d_out, d_out, i + 1 == nf, c.stream)) return rc;
+	}
+	if (c.fp && be_motion_filter(d_out, c.mf, (uint64_t)c.span, c.coded, c.stream)) return fail(-4, "filter launch failed");
+	for (size_t i = 0; i < ni; i++)
+		if (int rc = run_pass<float>(inv, inv->passes[i], (const float *)d_out, d_out, i + 1 == ni, c.stream)) return rc;
+	if (c.d_out8 && be_region_f32_to_u8(c.d_out8, d_out, c.mul8, c.ni3, c.sw3, c.sw3, c.stream)) return fail(-4, "launch failed");
+	return 0;
+}
+
+// the plans' pass lists, with the forward plan's last and the inverse plan's first pass in one column kernel where there is one
+int rt_run_passes(const RtCall &c)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
+	const Pass &F = *c.F, &I = *c.I;
+	float *const d_out = c.d_out;
+	void *const stream = c.stream;
+	const bool sweep_in = c.d_in8 && !c.u8_first;        // no fused load: one sweep
+	if (sweep_in && be_u8_to_f32(d_out, c.d_in8, (uint64_t)c.span, stream)) return fail(-4, "launch failed");
+	const float *d_in = sweep_in ? d_out : c.d_in;
+	for (size_t i = 0; i + 1 < nf; i++) {
+		const Pass &P = fwd->passes[i];
+		if (i == 0 && c.d_in8 && c.u8_first) {
+			U8IO io; io.in = c.d_in8; io.out = nullptr; io.mul = 1.0;
+			if (int rc = run_pass_u8(fwd, P, d_out, d_out, false, io, stream)) return rc;
+			continue;
+		}
+		if (int rc = run_pass<float>(fwd, P, P.first ? d_in : d_out, d_out, false, stream)) return rc;
+	}
+	const float *src = nf == 1 ? d_in : d_out;
+	const bool listed = F.has_spec && I.has_spec && F.spec.id == I.spec.id;
+	const bool compiled = !listed && F.jit && I.jit && F.jit_fn_rt && F.jit_type == I.jit_type;      // kernels compiled at plan time (jit_kernels.h)
+	const bool fusable = F.type == Pass::COL && I.type == Pass::COL && (listed || compiled) && F.spec_nwg == I.spec_nwg &&
+	                     F.hostloop.empty() && I.hostloop.empty() && (15u & ((uintptr_t)src | (uintptr_t)d_out)) == 0 && !fused_roundtrip_off();
+	PassArgs af, ai;
+	if (fusable) {
+		fill_args(af, F.spa, fwd, F, src, d_out, fwd->scale, Fuse());
+		fill_args(ai, I.spa, inv, I, (const float *)d_out, d_out, ni == 1 ? inv->scale : 1.0, Fuse());
+	}
+	if (fusable && is_plain_args(af) && is_plain_args(ai)) {      // (the fused kernel is the plain instantiation of both passes)
+		if (compiled) {
+			// parameters: (PassArgs af, PassArgs ai, FilterOp filt, unsigned long long *coded); FilterOp is the MotionFilter, nothing else
+			void *args[4] = {&af, &ai, (void *)&c.mf, (void *)&c.coded};
+			if (int rc = be_jit_launch_n(F.jit_fn_rt, args, F.spec_nwg, F.jit_nthr, stream)) return fail(-4, "kernel launch failed (fused roundtrip, compiled at plan time): backend code %d", rc);
+		} else if (int rc = be_launch_roundtrip(F.spec.id, af, ai, c.mf, c.coded, F.spec_nwg, stream)) return fail(-4, "kernel launch failed (fused roundtrip): backend code %d", rc);
+	} else {
+		if (int rc = run_pass<float>(fwd, F, src, d_out, true, stream)) return rc;
+		if (c.fp && be_motion_filter(d_out, c.mf, (uint64_t)c.span, c.coded, stream)) return fail(-4, "filter launch failed");
+		if (int rc = run_pass<float>(inv, I, (const float *)d_out, d_out, ni == 1, stream)) return rc;
+	}
+	for (size_t i = 1; i < ni; i++) {
+		const Pass &P = inv->passes[i];
+		if (i + 1 == ni && c.d_out8 && c.u8_last) {
+			U8IO io; io.in = nullptr; io.out = c.d_out8; io.mul = c.mul8;
+			if (int rc = run_pass_u8(inv, P, d_out, d_out, true, io, stream)) return rc;
+			continue;
+		}
+		if (int rc = run_pass<float>(inv, P, (const float *)d_out, d_out, i + 1 == ni, stream)) return rc;
+	}
+	if (c.d_out8 && !c.u8_last && be_f32_to_u8(c.d_out8, d_out, c.mul8, (uint64_t)c.span, stream)) return fail(-4, "launch failed");    // no fused store: one sweep
+	return 0;
+}
+
 // ---- a clip of frames in slices (motion's per-frame blocks, motion/motion.c:591,613-615: the frames are independent) ----
 // The three launches of the 8-bit roundtrip move the clip's float intermediate through HBM four times (2.1 GB for config 5's luma plane).  Walked
 // in slices of S frames -- 8-bit rows -> fused column roundtrip -> 8-bit rows per slice, every slice through the SAME S frames of the work
@@ -1683,9 +1897,20 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 constexpr size_t kSliceBytes = 100u << 20;        // per work area (two areas in flight: 200 MB of the cache's 256)
 constexpr int kSliceTileK = 8;
 
-int slice_frames(const dspfft_plan_s *fwd, const dspfft_plan_s *inv, const dspfft_motion_filter_params *fp, int nstreams)
+// the two slice switches, read once per process
+struct SliceSwitches { int forced, nstreams; };
+const SliceSwitches &slice_switches()
 {
-	static const int forced = []() { const char *e = getenv("DSPFFT_RT_SLICE"); return e ? atoi(e) : -1; }();
+	static const SliceSwitches s = []() {
+		const char *f = getenv("DSPFFT_RT_SLICE"), *n = getenv("DSPFFT_RT_STREAMS");
+		return SliceSwitches{f ? atoi(f) : -1, std::min(2, std::max(1, n ? atoi(n) : 2))};
+	}();
+	return s;
+}
+
+int slice_frames(const dspfft_plan_s *fwd, const dspfft_plan_s *inv, const dspfft_motion_filter_params *fp)
+{
+	const int forced = slice_switches().forced, nstreams = slice_switches().nstreams;
 	if (forced == 0 || fwd->rank != 2 || fwd->batches.size() != 1 || inv->batches.size() != 1 || fwd->passes.size() != 2 || inv->passes.size() != 2) return 0;
 	if (fwd->col_kpref || inv->col_kpref) return 0;                     // (a slice plan itself)
 	const Pass &F = fwd->passes[1], &I = inv->passes[0];
@@ -1703,6 +1928,12 @@ int slice_frames(const dspfft_plan_s *fwd, const dspfft_plan_s *inv, const dspff
 	return (int)std::min<long long>(S, b.n);
 }
 
+// a slice plan is planned as its parent was: under the parent's snapshot of the planner's switches and its planning effort
+struct EffortScope {
+	const int prev = t_plan_effort;
+	explicit EffortScope(int effort) { t_plan_effort = effort; }
+	~EffortScope() { t_plan_effort = prev; }
+};
 dspfft_plan_s *slice_plan(const dspfft_plan_s *of, int frames)
 {
 	dspfft_plan_s *pl = new dspfft_plan_s();
@@ -1710,217 +1941,92 @@ dspfft_plan_s *slice_plan(const dspfft_plan_s *of, int frames)
 	for (int a = 0; a < of->rank; a++) { pl->n[a] = of->n[a]; pl->kinds[a] = of->kinds[a]; pl->in0[a] = of->in0[a]; pl->out0[a] = of->out0[a]; pl->axes[a] = of->axes[a]; }
 	if (frames > 1) pl->batches.push_back(Dim{frames, of->batches[0].is, of->batches[0].os});
 	pl->col_kpref = kSliceTileK;
+	EnvScope env(of->plan_env);
+	EffortScope effort(of->plan_effort);
 	dspfft_plan out = nullptr;
 	return plan_finish(pl, &out, of->first_axis_first) ? nullptr : out;
 }
+// the parent's scales may have been set since its slice plans were made (dspfft_plan_set_scale / _set_axis_scale0)
+void follow_scales(std::initializer_list<dspfft_plan_s *> slices, const dspfft_plan_s *of)
+{
+	for (dspfft_plan_s *q : slices) if (q) { q->scale = of->scale; for (int a = 0; a < 2; a++) { q->in0[a] = of->in0[a]; q->out0[a] = of->out0[a]; } }
+}
+// From the fork on, the join of the library's stream: on every way out of roundtrip_sliced the caller's stream waits for what the side stream
+// was given, so that nothing of this call writes the caller's buffers once the caller's stream is through.  (Sets no error text: the first
+// error's stays.)
+struct SideJoin {
+	dspfft_plan_s::RtSlices *r;               // NULL: nothing to join (one stream, or joined already)
+	void *stream;
+	int join()
+	{
+		dspfft_plan_s::RtSlices *q = std::exchange(r, nullptr);
+		if (!q || !(be_event_record(q->ev_join, q->side) || be_stream_wait_event(stream, q->ev_join))) return 0;
+		be_stream_synchronize(q->side);
+		return -1;
+	}
+	~SideJoin() { join(); }
+};
 
 // returns 1 when the clip was run in slices, 0 when this call does not qualify (the caller runs it whole), < 0 on error
-int roundtrip_sliced(dspfft_plan fwd, dspfft_plan inv, float *d_work, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
-                     const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, const Dither *dither)
+int roundtrip_sliced(const RtCall &c, const Dither *dither)
 {
-	static const int nstreams = []() { const char *e = getenv("DSPFFT_RT_STREAMS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v > 2 ? 2 : v; }();
-	const int S = slice_frames(fwd, inv, fp, nstreams);
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const int S = slice_frames(fwd, inv, c.fp);
 	if (!S) return 0;
 	std::lock_guard<std::mutex> lock(fwd->rt_mutex);
+	const int total = fwd->batches[0].n, rem = total % S;
 	dspfft_plan_s::RtSlices *r = nullptr;
-	for (dspfft_plan_s::RtSlices &c : fwd->rt_slices) if (c.inv_of == inv && c.frames == S) r = &c;
+	for (const auto &q : fwd->rt_slices) if (q->inv_of == inv && q->frames == S) r = q.get();
 	if (!r) {
-		dspfft_plan_s::RtSlices c;
-		const int total = fwd->batches[0].n, rem = total % S;
-		c.inv_of = inv; c.frames = S;
-		c.fwd = slice_plan(fwd, S); c.inv = slice_plan(inv, S);
-		if (rem) { c.fwd_rem = slice_plan(fwd, rem); c.inv_rem = slice_plan(inv, rem); }
-		if (nstreams > 1) { c.side = be_stream_create(); c.ev_fork = be_order_event_create(); c.ev_join = be_order_event_create(); }
-		const bool ok = c.fwd && c.inv && (!rem || (c.fwd_rem && c.inv_rem)) && (nstreams == 1 || (c.side && c.ev_fork && c.ev_join));
-		if (!ok) {
-			dspfft_destroy_plan(c.fwd); dspfft_destroy_plan(c.inv); dspfft_destroy_plan(c.fwd_rem); dspfft_destroy_plan(c.inv_rem);
-			if (c.side) be_stream_destroy(c.side);
-			if (c.ev_fork) be_event_destroy(c.ev_fork);
-			if (c.ev_join) be_event_destroy(c.ev_join);
-			return 0;
-		}
-		fwd->rt_slices.push_back(c);
-		r = &fwd->rt_slices.back();
+		auto n = std::make_unique<dspfft_plan_s::RtSlices>();
+		const bool two = slice_switches().nstreams > 1;
+		n->inv_of = inv; n->frames = S;
+		n->fwd = slice_plan(fwd, S); n->inv = slice_plan(inv, S);
+		if (rem) { n->fwd_rem = slice_plan(fwd, rem); n->inv_rem = slice_plan(inv, rem); }
+		if (two) { n->side = be_stream_create(); n->ev_fork = be_order_event_create(); n->ev_join = be_order_event_create(); }
+		bool ok = n->fwd && n->inv && (!rem || (n->fwd_rem && n->inv_rem)) && (!two || (n->side && n->ev_fork && n->ev_join));
+		// slices without the 8-bit row kernels would take another, slower path than the clip does: the clip then runs whole
+		for (dspfft_plan_s *q : {n->fwd, n->fwd_rem}) ok = ok && (!q || pass_has_u8(q, q->passes.front()));
+		for (dspfft_plan_s *q : {n->inv, n->inv_rem}) ok = ok && (!q || pass_has_u8(q, q->passes.back()));
+		if (!ok) return 0;
+		r = n.get();
+		fwd->rt_slices.push_back(std::move(n));
 	}
-	// the parents' scales may have been set since (dspfft_plan_set_scale / _set_axis_scale0)
-	for (dspfft_plan_s *q : {r->fwd, r->fwd_rem}) if (q) { q->scale = fwd->scale; for (int a = 0; a < 2; a++) { q->in0[a] = fwd->in0[a]; q->out0[a] = fwd->out0[a]; } }
-	for (dspfft_plan_s *q : {r->inv, r->inv_rem}) if (q) { q->scale = inv->scale; for (int a = 0; a < 2; a++) { q->in0[a] = inv->in0[a]; q->out0[a] = inv->out0[a]; } }
-	const int total = fwd->batches[0].n;
+	follow_scales({r->fwd, r->fwd_rem}, fwd);
+	follow_scales({r->inv, r->inv_rem}, inv);
 	const long long fin = fwd->batches[0].is, fwk = fwd->batches[0].os, fout = inv->batches[0].os;
-	const bool two = nstreams > 1 && r->side;
-	if (two && (be_event_record(r->ev_fork, stream) || be_stream_wait_event(r->side, r->ev_fork))) return fail(-4, "stream fork failed");
+	const bool two = r->side != nullptr;
+	if (two && (be_event_record(r->ev_fork, c.stream) || be_stream_wait_event(r->side, r->ev_fork))) return fail(-4, "stream fork failed");
+	SideJoin side = {two ? r : nullptr, c.stream};
 	int k = 0;
 	for (int f0 = 0; f0 < total; f0 += S, k++) {
-		const bool last = total - f0 < S;
-		void *st = (two && (k & 1)) ? r->side : stream;
-		float *work = d_work + ((two && (k & 1)) ? (long long)S * fwk : 0);
+		const bool last = total - f0 < S, odd = two && (k & 1);
 		// dithered: each slice's planes (whole frames) are dithered on the slice's stream before its work area is reused
 		Dither ds;
 		if (dither) { ds = *dither; ds.out8 += (long long)f0 * fout; }
-		if (int rc = roundtrip_core(last ? r->fwd_rem : r->fwd, last ? r->inv_rem : r->inv, nullptr, work, d_in8 + (long long)f0 * fin,
-		                            d_out8 ? d_out8 + (long long)f0 * fout : nullptr, mul8, fp, d_coeffs_coded, st, false, dither ? &ds : nullptr)) return rc;
+		if (int rc = roundtrip_core(last ? r->fwd_rem : r->fwd, last ? r->inv_rem : r->inv, nullptr, c.d_out + (odd ? (long long)S * fwk : 0), c.d_in8 + (long long)f0 * fin,
+		                            c.d_out8 ? c.d_out8 + (long long)f0 * fout : nullptr, c.mul8, c.fp, c.coded, odd ? r->side : c.stream, false, dither ? &ds : nullptr)) return rc;
 	}
-	if (two && (be_event_record(r->ev_join, r->side) || be_stream_wait_event(stream, r->ev_join))) return fail(-4, "stream join failed");
-	return 1;
+	return side.join() ? fail(-4, "stream join failed") : 1;
 }
 
-// d_in8 / d_out8 non-NULL: 8-bit samples at the two ends (dspfft_execute_roundtrip_u8), d_out is then the float work buffer.
 // dither non-NULL (d_out8 NULL): the inverse transform ends in d_out as floats and the dither kernel stores dither->out8 from there.
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
                    const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice, const Dither *dither)
 {
-	if (!fwd || !inv || !(d_in || d_in8) || !d_out) return fail(-1, "null plan or buffer");
-	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
-	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
-	const Pass &F = fwd->passes[nf - 1], &I = inv->passes[0];
-	bool differs = fwd->rank != inv->rank;
-	for (int a = 0; !differs && a < fwd->rank; a++) differs = fwd->n[a] != inv->n[a];
-	// (plans whose blocks go through the fused block pass have no pass order to agree on)
-	if (fwd->rank != inv->rank || fwd->howmany != inv->howmany || (!differs && F.axis != I.axis && !block_roundtrip_ok(fwd, inv)))
-		return fail(-1, "the forward plan's last pass and the inverse plan's first pass must run along the same axis (create the inverse with dspfft_plan_many_r2r_ordered(..., 1))");
-	// motion's `scaled != block` (motion.c:535-552): the inverse runs over DIFFERENT extents inside the same embedding -- larger:
-	// the spectrum is zero-padded (band-limited upscale), smaller: truncated (downscale)
-	bool rescale = false;
-	for (int a = 0; a < fwd->rank; a++) {
-		if (fwd->axes[a].os != inv->axes[a].is || inv->axes[a].is != inv->axes[a].os || fwd->kinds[a] != DSPFFT_REDFT10 || inv->kinds[a] != DSPFFT_REDFT01)
-			return fail(-1, "roundtrip: the inverse must be REDFT01, in place, on the forward (REDFT10) plan's output layout");
-		rescale = rescale || fwd->n[a] != inv->n[a];
+	RtCall c = {fwd, inv, d_in, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream};
+	if (int rc = rt_check(c)) return rc;
+	int rc = 0;
+	if (c.block) rc = rt_run_block(c);
+	else if (c.rescale) rc = rt_run_rescale(c);
+	else {
+		if (may_slice && d_in8 && (d_out8 || dither) && c.u8_first && c.u8_last && c.F->axis == c.I->axis && (15u & (uintptr_t)d_out) == 0 && !fused_roundtrip_off())
+			rc = roundtrip_sliced(c, dither);
+		if (rc) return rc < 0 ? rc : 0;          // in slices: every slice has stored or dithered its own frames
+		rc = rt_run_passes(c);
 	}
-	if (rescale && (!fwd->batches.empty() || !inv->batches.empty())) return fail(-2, "roundtrip with different forward / inverse extents takes one block per call (howmany = 1)");
-	if (rescale)
-		for (int a = 0; a < fwd->rank; a++)
-			if (fwd->axes[a].is != fwd->axes[a].os) return fail(-2, "roundtrip with different forward / inverse extents needs ONE embedding for input, work and output (motion.c:535-552)");
-	if (fwd->batches.size() != inv->batches.size()) return fail(-1, "roundtrip: batch layouts differ");
-	for (size_t b = 0; b < fwd->batches.size(); b++)
-		if (fwd->batches[b].n != inv->batches[b].n || fwd->batches[b].os != inv->batches[b].is || inv->batches[b].is != inv->batches[b].os) return fail(-1, "roundtrip: batch layouts differ");
-	MotionFilter mf;
-	memset(&mf, 0, sizeof mf);
-	if (fp) {
-		if (fp->preserve_dc < 0 || fp->preserve_dc > 2 || fp->minbuf_hw[0] < 1 || fp->minbuf_hw[1] < 1 || fp->block_depth < 1) return fail(-1, "bad filter parameters");
-		mf.ad = fp->active[0]; mf.ah = fp->active[1]; mf.aw = fp->active[2]; mf.mh = fp->minbuf_hw[0]; mf.mw = fp->minbuf_hw[1];
-		mf.b0d = fp->band_begin[0]; mf.b0h = fp->band_begin[1]; mf.b0w = fp->band_begin[2];
-		mf.b1d = fp->band_end[0]; mf.b1h = fp->band_end[1]; mf.b1w = fp->band_end[2];
-		mf.damp = fp->damp; mf.boost = fp->boost; mf.thr_lo = fp->threshold_lo; mf.thr_hi = fp->threshold_hi;
-		mf.preserve_dc = fp->preserve_dc; mf.grey_add = fp->grey_add; mf.quantizer = fp->quantizer; mf.enabled = 1;
-		motion_filter_set_divs(mf, fp->block_depth);
-	}
-	// extent of the working buffer in elements (the filter addresses it with 32-bit offsets)
-	long long span = 1;
-	for (int a = 0; a < fwd->rank; a++) span += (long long)(std::max(fwd->n[a], inv->n[a]) - 1) * fwd->axes[a].os;
-	for (const Dim &b : fwd->batches) span += (long long)(b.n - 1) * b.os;
-	if (fp && span >= (1ll << 31)) return fail(-2, "filtered roundtrip addresses the buffer with 31-bit offsets: buffer too large");
-	// region geometry of the two ends (rank padded to 3 with unit extents)
-	int nf3[3] = {1, 1, 1}, ni3[3] = {1, 1, 1};
-	long long sw3[3] = {0, 0, 0}, si3[3] = {0, 0, 0};
-	for (int a = 0; a < fwd->rank; a++) {
-		const int k = 3 - fwd->rank + a;
-		nf3[k] = fwd->n[a]; ni3[k] = inv->n[a]; sw3[k] = fwd->axes[a].os; si3[k] = fwd->axes[a].is;
-	}
-	// small blocks: everything in one pass over the data
-	if (!rescale && block_roundtrip_ok(fwd, inv)) {
-		const uintptr_t pin = d_in8 ? (uintptr_t)d_in8 : (uintptr_t)d_in, pout = d_out8 ? (uintptr_t)d_out8 : (uintptr_t)d_out;
-		if (!((d_in8 ? 3u : 15u) & pin) && !((d_out8 ? 3u : 15u) & pout)) {
-			BlockRtArgs a;
-			static_cast<BlockGeom &>(a) = fwd->blk;
-			const BlockGeom &o = inv->blk;
-			a.sy_out = o.sy_out; a.sz_out = o.sz_out; a.sxb_out = o.sxb_out;
-			for (int d = 0; d < o.nd; d++) a.bos[d] = o.bos[d];
-			a.in = d_in8 ? nullptr : d_in; a.out = d_out8 ? nullptr : d_out; a.in8 = d_in8; a.out8 = d_out8; a.mul8 = mul8;
-			block_scales(fwd, a.f); block_scales(inv, a.i);
-			a.filt = mf; a.coded = d_coeffs_coded;
-			if (int rc = be_launch_block_roundtrip(a, fwd->blk_nwg, fwd->blk_lds, stream)) return fail(-4, "kernel launch failed (fused block roundtrip): backend code %d", rc);
-			return dither ? dither_store(inv, d_out, *dither, stream) : 0;
-		}
-	}
-	// the standalone filter finds a coefficient's position from its offset in a block-major embedding (minbuf_hw, block_depth); the
-	// blocks of a volume lying side by side are filtered by the fused block pass only, which knows each block's own coordinates
-	if (fp && fwd->has_block && !fwd->blk.rows_fast)
-		return fail(-2, "filtered roundtrip over the blocks of a volume needs the fused block pass: matching forward / inverse plans and 16-byte (8-bit: 4-byte) aligned buffers");
-	if (rescale) {
-		// one block, unfused: zero the working buffer (motion.c:619), load the block region, forward, filter, inverse over the
-		// scaled region, store it.  In place on a float buffer the caller has zeroed everything outside the block itself.
-		if (d_in8) {
-			if (be_zero(d_out, (size_t)span * sizeof(float), stream) || be_region_u8_to_f32(d_out, d_in8, nf3, sw3, si3, stream)) return fail(-4, "launch failed");
-			d_in = d_out;
-		} else if (d_in != d_out) {
-			if (be_zero(d_out, (size_t)span * sizeof(float), stream)) return fail(-4, "launch failed");
-		}
-		for (size_t i = 0; i < nf; i++) {
-			const Pass &P = fwd->passes[i];
-			if (int rc = run_pass<float>(fwd, P, (P.first && !d_in8) ? d_in : d_out, d_out, i + 1 == nf, stream)) return rc;
-		}
-		if (fp && be_motion_filter(d_out, mf, (uint64_t)span, d_coeffs_coded, stream)) return fail(-4, "filter launch failed");
-		for (size_t i = 0; i < ni; i++)
-			if (int rc = run_pass<float>(inv, inv->passes[i], (const float *)d_out, d_out, i + 1 == ni, stream)) return rc;
-		if (d_out8 && be_region_f32_to_u8(d_out8, d_out, mul8, ni3, sw3, sw3, stream)) return fail(-4, "launch failed");
-		return dither ? dither_store(inv, d_out, *dither, stream) : 0;
-	}
-	if (d_in8 || d_out8) {
-		// the 8-bit buffers share the plans' element layout; the unfused conversions below walk whole spans
-		if (nf < 2 || ni < 2) return fail(-2, "8-bit roundtrip needs at least two transformed axes");
-		long long ispan = 1;
-		for (int a = 0; a < fwd->rank; a++) ispan += (long long)(fwd->n[a] - 1) * fwd->axes[a].is;
-		for (const Dim &b : fwd->batches) ispan += (long long)(b.n - 1) * b.is;
-		if (d_out8 && !pass_has_u8(inv, inv->passes[ni - 1])) {
-			// the output conversion will be one sweep over the whole span, which must then hold nothing but samples
-			long long dense = 1;
-			for (int a = 0; a < fwd->rank; a++) dense *= fwd->n[a];
-			for (const Dim &b : fwd->batches) dense *= b.n;
-			if (dense != span) return fail(-2, "8-bit output without a planar specialised row pass needs a dense work layout");
-		}
-		if (d_in8 && !pass_has_u8(fwd, fwd->passes[0])) {
-			if (ispan != span) return fail(-2, "8-bit input without a planar specialised row pass needs identical input and work layouts");
-			if (be_u8_to_f32(d_out, d_in8, (uint64_t)span, stream)) return fail(-4, "launch failed");
-			d_in = d_out; d_in8 = nullptr;
-		}
-	}
-	if (may_slice && d_in8 && (d_out8 || dither) && pass_has_u8(fwd, fwd->passes[0]) && pass_has_u8(inv, inv->passes[ni - 1]) && F.axis == I.axis &&
-	    (15u & (uintptr_t)d_out) == 0 && !(getenv("DSPFFT_NO_FUSED_ROUNDTRIP") && *getenv("DSPFFT_NO_FUSED_ROUNDTRIP") == '1')) {
-		const int rc = roundtrip_sliced(fwd, inv, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream, dither);
-		if (rc) return rc < 0 ? rc : 0;
-	}
-	for (size_t i = 0; i + 1 < nf; i++) {
-		const Pass &P = fwd->passes[i];
-		if (i == 0 && d_in8) {
-			U8IO io; io.in = d_in8; io.out = nullptr; io.mul = 1.0;
-			if (int rc = run_pass_u8(fwd, P, d_out, d_out, false, io, stream)) return rc;
-			continue;
-		}
-		if (int rc = run_pass<float>(fwd, P, P.first ? d_in : d_out, d_out, false, stream)) return rc;
-	}
-	const float *src = nf == 1 ? d_in : d_out;
-	const bool listed = F.has_spec && I.has_spec && F.spec.id == I.spec.id;
-	const bool compiled = !listed && F.jit && I.jit && F.jit_fn_rt && F.jit_type == I.jit_type;      // kernels compiled at plan time (jit_kernels.h)
-	const bool fusable = F.type == Pass::COL && I.type == Pass::COL && (listed || compiled) && F.spec_nwg == I.spec_nwg &&
-	                     F.hostloop.empty() && I.hostloop.empty() && (15u & ((uintptr_t)src | (uintptr_t)d_out)) == 0 &&
-	                     !(getenv("DSPFFT_NO_FUSED_ROUNDTRIP") && *getenv("DSPFFT_NO_FUSED_ROUNDTRIP") == '1');
-	PassArgs af, ai;
-	if (fusable) {
-		fill_args(af, F.spa, fwd, F, src, d_out, fwd->scale, Fuse());
-		fill_args(ai, I.spa, inv, I, (const float *)d_out, d_out, ni == 1 ? inv->scale : 1.0, Fuse());
-	}
-	if (fusable && is_plain_args(af) && is_plain_args(ai)) {      // (the fused kernel is the plain instantiation of both passes)
-		if (compiled) {
-			// parameters: (PassArgs af, PassArgs ai, FilterOp filt, unsigned long long *coded); FilterOp is the MotionFilter, nothing else
-			void *args[4] = {&af, &ai, &mf, &d_coeffs_coded};
-			if (int rc = be_jit_launch_n(F.jit_fn_rt, args, F.spec_nwg, F.jit_nthr, stream)) return fail(-4, "kernel launch failed (fused roundtrip, compiled at plan time): backend code %d", rc);
-		} else if (int rc = be_launch_roundtrip(F.spec.id, af, ai, mf, d_coeffs_coded, F.spec_nwg, stream)) return fail(-4, "kernel launch failed (fused roundtrip): backend code %d", rc);
-	} else {
-		if (int rc = run_pass<float>(fwd, F, src, d_out, true, stream)) return rc;
-		if (fp && be_motion_filter(d_out, mf, (uint64_t)span, d_coeffs_coded, stream)) return fail(-4, "filter launch failed");
-		if (int rc = run_pass<float>(inv, I, (const float *)d_out, d_out, ni == 1, stream)) return rc;
-	}
-	for (size_t i = 1; i < ni; i++) {
-		const Pass &P = inv->passes[i];
-		if (i + 1 == ni && d_out8 && pass_has_u8(inv, P)) {
-			U8IO io; io.in = nullptr; io.out = d_out8; io.mul = mul8;
-			if (int rc = run_pass_u8(inv, P, d_out, d_out, true, io, stream)) return rc;
-			return 0;
-		}
-		if (int rc = run_pass<float>(inv, P, (const float *)d_out, d_out, i + 1 == ni, stream)) return rc;
-	}
-	if (d_out8 && be_f32_to_u8(d_out8, d_out, mul8, (uint64_t)span, stream)) return fail(-4, "launch failed");    // no fused store: one sweep
-	return dither ? dither_store(inv, d_out, *dither, stream) : 0;
+	if (rc || !dither) return rc;
+	return dither_store(inv, d_out, *dither, stream);
 }
 }  // namespace
 
@@ -2102,12 +2208,6 @@ extern "C" void dspfft_destroy_plan(dspfft_plan pl)
 	for (Pass &P : pl->passes) P.tab.release();
 	for (Pass &P : pl->split) P.tab.release();
 	be_free(pl->zflags); be_free(pl->zpage); be_free(pl->zranges); be_free(pl->eids);
-	for (dspfft_plan_s::RtSlices &r : pl->rt_slices) {
-		dspfft_destroy_plan(r.fwd); dspfft_destroy_plan(r.inv); dspfft_destroy_plan(r.fwd_rem); dspfft_destroy_plan(r.inv_rem);
-		if (r.side) be_stream_destroy(r.side);
-		if (r.ev_fork) be_event_destroy(r.ev_fork);
-		if (r.ev_join) be_event_destroy(r.ev_join);
-	}
 	delete pl;
 }
 
@@ -2119,10 +2219,11 @@ extern "C" int dspfft_plan_describe(dspfft_plan pl, char *buf, size_t buflen)
 	for (const Pass &P : pl->split) { s += P.desc; s += "\n"; }
 	if (pl->has_block) { s += pl->blk_desc; s += "\n"; }
 	for (const Pass &P : pl->passes) { if (!pl->split.empty() || pl->has_block) s += "plain "; s += P.desc; if (!P.hostloop.empty()) s += " +hostloop"; s += "\n"; }
-	for (const dspfft_plan_s::RtSlices &r : pl->rt_slices) {          // (present once dspfft_execute_roundtrip_u8 has walked a clip in slices)
+	std::lock_guard<std::mutex> lock(pl->rt_mutex);                  // (another thread's first roundtrip over a clip may be adding to rt_slices)
+	for (const auto &r : pl->rt_slices) {                            // (present once dspfft_execute_roundtrip_u8 has walked a clip in slices)
 		char b[256];
-		snprintf(b, sizeof b, "roundtrip_u8 in slices of %d frames (last: %d) on %d stream(s): ", r.frames, r.fwd_rem ? r.fwd_rem->howmany : r.frames, r.side ? 2 : 1);
-		s += b; s += r.fwd->passes.back().desc; s += "\n";
+		snprintf(b, sizeof b, "roundtrip_u8 in slices of %d frames (last: %d) on %d stream(s): ", r->frames, r->fwd_rem ? r->fwd_rem->howmany : r->frames, r->side ? 2 : 1);
+		s += b; s += r->fwd->passes.back().desc; s += "\n";
 	}
 	snprintf(buf, buflen, "%s", s.c_str());
 	return 0;

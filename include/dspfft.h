@@ -249,7 +249,14 @@ int dspfft_execute_roundtrip(dspfft_plan fwd, dspfft_plan inv, const float *d_in
  * layout.  When the first forward pass and the last inverse pass are planar specialised row passes they read the
  * bytes and write quantise(value * out_mul) themselves (5 B/sample each instead of 13); otherwise the conversions
  * run as separate sweeps (dspfft_u8_to_f32 / dspfft_f32_to_u8), which requires input, work and output layouts to be
- * identical and dense. */
+ * identical and dense.
+ * A clip of frames (2-D plans with one batch level, a column length that has a narrow-tile kernel, 8-bit row kernels at both ends) runs
+ * in slices of frames whose float intermediate the last-level cache holds.  The first call that qualifies builds plans for a slice,
+ * which the forward plan owns until it is destroyed: device allocations of their own, and -- unless DSPFFT_RT_STREAMS=1 -- one stream
+ * and two events of the library's, on which every other slice runs; the call forks from hip_stream and joins it again before it
+ * returns, also when it fails.  Calls on the same plan pair serialise on a mutex while they enqueue (they may use different buffers
+ * and streams).  dspfft_plan_describe of the forward plan lists the slices from then on, in one more line.  The two switches,
+ * DSPFFT_RT_SLICE (frames per slice; 0: never in slices) and DSPFFT_RT_STREAMS, are process-wide: read once, at the first such call. */
 int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
                                 const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
 /* dspfft_execute_roundtrip_u8 with motion's -d: the final 8-bit store replaced by the dithered one (dspfft_motion_dither_u8 below, over the

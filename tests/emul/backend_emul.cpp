@@ -8,6 +8,10 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <stdio.h>
+#include <map>
+#include <mutex>
+#include <string>
 #include <vector>
 #include "backend.h"
 #include "dct_spec.h"
@@ -23,16 +27,48 @@ void be_free(void *p) { free(p); }
 int be_upload(void *dst, const void *src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
 size_t be_max_lds() { const char *e = getenv("DSPFFT_EMUL_LDS"); return e ? (size_t)atol(e) : 160 * 1024; }
 const char *be_name() { return "cpu-emulation (tests only)"; }
-void *be_event_create() { return malloc(1); }
-void be_event_destroy(void *e) { free(e); }
-int be_event_record(void *, void *) { return 0; }
+// TEST-ONLY trace of what the engine asks of streams and events (dspfft_emul_trace): "record eE sS", "wait sS eE" and, from
+// launch_col_roundtrip, "roundtrip sS ok|fail".  Streams and events are numbered by creation from 1; the caller's stream (any pointer this
+// backend did not hand out, NULL included) is 0.
+static std::mutex g_trace_mutex;
+static std::string g_trace;
+static std::map<void *, int> g_stream_no, g_event_no;
+static int g_streams = 0, g_events = 0, g_roundtrips = 0;
+static int number_of(const std::map<void *, int> &m, void *p) { auto it = m.find(p); return it == m.end() ? 0 : it->second; }
+static void trace(const char *what, char a, int x, char b, int y)
+{
+	char line[64];
+	snprintf(line, sizeof line, "%s %c%d %c%d\n", what, a, x, b, y);
+	g_trace += line;
+}
+static void *new_event() { void *e = malloc(1); std::lock_guard<std::mutex> l(g_trace_mutex); g_event_no[e] = ++g_events; return e; }
+void *be_event_create() { return new_event(); }
+void be_event_destroy(void *e) { { std::lock_guard<std::mutex> l(g_trace_mutex); g_event_no.erase(e); } free(e); }
+int be_event_record(void *e, void *s) { std::lock_guard<std::mutex> l(g_trace_mutex); trace("record", 'e', number_of(g_event_no, e), 's', number_of(g_stream_no, s)); return 0; }
 int be_event_synchronize(void *) { return 0; }
 int be_event_elapsed_ms(void *, void *, float *ms) { *ms = 0.f; return 0; }
-void *be_stream_create() { return malloc(1); }
-void be_stream_destroy(void *s) { free(s); }
+void *be_stream_create() { void *s = malloc(1); std::lock_guard<std::mutex> l(g_trace_mutex); g_stream_no[s] = ++g_streams; return s; }
+void be_stream_destroy(void *s) { { std::lock_guard<std::mutex> l(g_trace_mutex); g_stream_no.erase(s); } free(s); }
 int be_stream_synchronize(void *) { return 0; }
-void *be_order_event_create() { return malloc(1); }
-int be_stream_wait_event(void *, void *) { return 0; }
+void *be_order_event_create() { return new_event(); }
+int be_stream_wait_event(void *s, void *e) { std::lock_guard<std::mutex> l(g_trace_mutex); trace("wait", 's', number_of(g_stream_no, s), 'e', number_of(g_event_no, e)); return 0; }
+// DSPFFT_EMUL_FAIL_ROUNDTRIP=k: the k-th fused column roundtrip of the process returns an error code instead of running (an ordinary return
+// value; read at every launch, so a test can clear it)
+static int roundtrip_launch_fails(void *stream)
+{
+	const char *e = getenv("DSPFFT_EMUL_FAIL_ROUNDTRIP");
+	std::lock_guard<std::mutex> l(g_trace_mutex);
+	const bool bad = ++g_roundtrips == (e ? atoi(e) : 0);
+	g_trace += "roundtrip s" + std::to_string(number_of(g_stream_no, stream)) + (bad ? " fail\n" : " ok\n");
+	return bad ? 1 : 0;
+}
+// the trace so far, NUL-terminated and cut to len; returns its full length
+extern "C" size_t dspfft_emul_trace(char *buf, size_t len)
+{
+	std::lock_guard<std::mutex> l(g_trace_mutex);
+	if (buf && len) snprintf(buf, len, "%s", g_trace.c_str());
+	return g_trace.size();
+}
 
 #define PHASE(stmt) for (int tid = 0; tid < nthr; tid++) { stmt; }
 
@@ -465,8 +501,9 @@ struct FilterOp {
 	}
 };
 template <class S>
-int launch_col_roundtrip(const PassArgs &af, const PassArgs &ai, const MotionFilter &filt, unsigned long long *coded, int nwork, void *)
+int launch_col_roundtrip(const PassArgs &af, const PassArgs &ai, const MotionFilter &filt, unsigned long long *coded, int nwork, void *stream)
 {
+	if (roundtrip_launch_fails(stream)) return 1;
 	std::vector<unsigned char> lds(S::LDS + 32);
 	typename S::V *buf = (typename S::V *)(((uintptr_t)lds.data() + 15) & ~(uintptr_t)15);
 	FilterOp f; f.p = filt;

@@ -1,7 +1,8 @@
 """GPU (-m gpu): dspfft_execute_roundtrip_u8 over a clip in slices (engine.cpp roundtrip_sliced) against the same clip in three launches, through the C ABI:
 bytes and the count of coded coefficients equal -- with the quantiser alone (motion --quant), with the position-dependent filter (band, damp / boost, threshold,
 DC rule) and with a filter block depth > 1, where a slice must start on a block boundary because the filter finds a frame's place in its block from its offset in
-the work area (motion/motion.c:591,613-615,683-744).  The switches are read once per process: every setting is a child process."""
+the work area (motion/motion.c:591,613-615,683-744).  The slice plans follow the scales their parents are given between two runs.  The switches are read
+once per process: every setting is a child process."""
 import os
 import subprocess
 import sys
@@ -36,15 +37,22 @@ torch.cuda.synchronize()
 d = fwd.describe()
 print("RESULT", "%%08x" %% zlib.crc32(dst.cpu().numpy().tobytes()), int(coded.item()), "sliced" if "roundtrip_u8 in slices of" in d else "whole",
       d.split("roundtrip_u8 in slices of")[-1].split(":")[0].strip().replace(" ", "_") if "roundtrip_u8 in slices of" in d else "-")
+if %(rescale)d:
+    # other scales, so that the quantiser sees other magnitudes
+    fwd.set_scale(3.0); inv.set_scale(1.0 / 3.0 / (4.0 * h * w))
+    coded.zero_()
+    fwd.roundtrip_u8(inv, src.data_ptr(), dst.data_ptr(), work.data_ptr(), 1.0, filter=flt, d_coded=coded.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    print("SECOND", "%%08x" %% zlib.crc32(dst.cpu().numpy().tobytes()), int(coded.item()))
 '''
 
 
-def run(env, **kw):
+def run(env, rescale=0, **kw):
     e = dict(os.environ); e.update(env)
-    r = subprocess.run([sys.executable, "-c", CHILD % dict(root=os.path.dirname(HERE), **kw)], env=e, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, "-c", CHILD % dict(root=os.path.dirname(HERE), rescale=rescale, **kw)], env=e, capture_output=True, text=True, timeout=900)
     lines = [x for x in r.stdout.splitlines() if x.startswith("RESULT")]
     assert lines, r.stderr[-2000:]
-    return lines[0].split()[1:]
+    return lines[0].split()[1:] + ([x for x in r.stdout.splitlines() if x.startswith("SECOND")][0].split()[1:] if rescale else [])
 
 
 @pytest.mark.parametrize("w,frames,bd,general", [(1920, 64, 1, 0), (960, 40, 1, 1), (960, 48, 4, 1)])
@@ -58,3 +66,14 @@ def test_sliced_clip_is_the_three_launch_clip(w, frames, bd, general):
         assert got[:2] == whole[:2], (env, got, whole)
         if bd > 1:                       # slices start on block boundaries
             assert int(got[3].split("_")[0]) % bd == 0, got
+
+
+def test_slices_follow_scales_set_between_runs():
+    """run, set other scales on both plans, run again: the second run in slices is the second run of the three-launch clip, and the quantiser, seeing
+    other magnitudes, codes another number of coefficients than in the first"""
+    kw = dict(w=960, frames=16, bd=1, general=0, rescale=1)
+    whole = run({"DSPFFT_RT_SLICE": "0"}, **kw)
+    got = run({"DSPFFT_RT_SLICE": "4", "DSPFFT_RT_STREAMS": "2"}, **kw)
+    assert whole[2] == "whole" and got[2] == "sliced", (whole, got)
+    assert got[:2] == whole[:2] and got[4:] == whole[4:] and len(got) == 6, (got, whole)
+    assert int(got[5]) != int(got[1]) and int(got[5]) > 0, got
