@@ -29,6 +29,8 @@ SYMBOLS = [
     "dspfft_zoomanim_create", "dspfft_zoomanim_work_floats", "dspfft_zoomanim_set_coeffs", "dspfft_zoomanim_execute", "dspfft_zoomanim_destroy", "dspfft_zoomanim_last_error",
     "dspfft_scanframes_create", "dspfft_scanframes_frame_floats", "dspfft_scanframes_begin", "dspfft_scanframes_mark_range", "dspfft_scanframes_mark_coords",
     "dspfft_scanframes_compose", "dspfft_scanframes_parity", "dspfft_scanframes_destroy",
+    "dspfft_trc_from_name", "dspfft_trc_name", "dspfft_trc_apply_f32", "dspfft_scanframes_set_trc", "dspfft_zoomanim_set_trc",
+    "dspfft_motion_load_f32_linear", "dspfft_motion_store_f32_linear",
     "dspfft_applybasis_work_floats", "dspfft_applybasis_partsums",
     "dspfft_applybasis_work_floats_ex", "dspfft_applybasis_partsums_ex", "dspfft_applybasis_render",
     "dspfft_motion_load_u8", "dspfft_motion_store_u8", "dspfft_motion_load_f32", "dspfft_motion_store_f32", "dspfft_motion_topn_work_bytes", "dspfft_motion_topn", "dspfft_motion_last_error", "dspfft_motion_dither_u8",
@@ -162,6 +164,15 @@ def bind(lib):
     lib.dspfft_scanframes_parity.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     lib.dspfft_scanframes_destroy.argtypes = [vp]
     lib.dspfft_scanframes_destroy.restype = None
+    if hasattr(lib, "dspfft_trc_from_name"):     # (absent from a build of an earlier commit named by DSPFFT_LIB_PATH for an A/B run)
+        lib.dspfft_trc_from_name.argtypes = [C.c_char_p]
+        lib.dspfft_trc_name.argtypes = [C.c_int]
+        lib.dspfft_trc_name.restype = C.c_char_p
+        lib.dspfft_trc_apply_f32.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, vp]
+        lib.dspfft_scanframes_set_trc.argtypes = [vp, C.c_int]
+        lib.dspfft_zoomanim_set_trc.argtypes = [vp, C.c_int]
+        lib.dspfft_motion_load_f32_linear.argtypes = [vp, vp, ip, ip, C.c_int, vp]
+        lib.dspfft_motion_store_f32_linear.argtypes = [vp, vp, ip, ip, C.c_double, C.c_double, C.c_int, vp]
     if hasattr(lib, "dspfft_zoom_product"):      # HIP-only entry points (absent from the CPU emulation used in tests)
         lib.dspfft_zoom_ncomponents.restype = C.c_size_t
         lib.dspfft_zoom_ncomponents.argtypes = [C.c_double, C.c_double, C.c_size_t]

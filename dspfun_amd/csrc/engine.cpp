@@ -26,6 +26,7 @@
 #include "backend.h"
 #include "scan_frame_core.h"
 #include "zoom_anim_core.h"
+#include "trc_core.h"
 
 using namespace dspfft;
 
@@ -38,7 +39,11 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_launch(
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_scanframes_launch(dspfft::SfOp *o, char *err, size_t errlen);
 // zoom_anim.hip's launcher (the overlay and planar store of dspfft_zoomanim_execute).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_zoomanim_finish_launch(float *d_out, const float *src, const dspfft::ZaOverlay *o,
-                                                                                          int planar, void *stream, char *err, size_t errlen);
+                                                                                          int planar, int trc, void *stream, char *err, size_t errlen);
+// pointwise.hip's and motion_ops.hip's launchers behind dspfft_trc_apply_f32 and dspfft_motion_{load,store}_f32_linear.  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_trc_apply_launch(float *d_dst, const float *d_src, uint64_t len, int trc, int inverse, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_motion_linear_launch(float *d_dst, const float *d_src, const int n[3], const int minbuf_hw[2], int store,
+                                                                                        double scalefactor, double normalization, int trc, void *stream);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -1556,7 +1561,7 @@ extern "C" int dspfft_transpose_f32(float *d_out, long long out_pitch, const flo
 // largest extents a frame can need (nc = w, h; y lines w 3) and each frame running on its own (cw, ch) <= (w, h).  The coefficients are
 // transposed once (set_coeffs); a frame reads the first cw 3 lines and the first ch entries of each.
 struct dspfft_zoomanim_s {
-	int w, h, type, vw, vh;
+	int w, h, type, vw, vh, trc;
 	bool coeffs_set;
 	float *Ct;                       // the coefficient block transposed: Ct[(u, c)][v], w 3 lines of h
 	dspfft_cztrows rows_y, rows_x;
@@ -1573,7 +1578,7 @@ extern "C" int dspfft_zoomanim_create(dspfft_zoomanim *out, int w, int h, int ty
 	const long long big = vh > h ? vh : h;
 	if ((long long)w * 3 * big >= (1ll << 31) || (long long)vw * vh * 3 >= (1ll << 31)) return fail(-2, "frame too large for 31-bit strides");
 	dspfft_zoomanim z = new dspfft_zoomanim_s();
-	z->w = w; z->h = h; z->type = type; z->vw = vw; z->vh = vh; z->coeffs_set = false;
+	z->w = w; z->h = h; z->type = type; z->vw = vw; z->vh = vh; z->trc = 0; z->coeffs_set = false;
 	z->rows_y = z->rows_x = nullptr;
 	z->Ct = (float *)be_alloc((size_t)w * 3 * h * sizeof(float));
 	if (!z->Ct) { delete z; return fail(-3, "no device memory for the transposed coefficients"); }
@@ -1610,10 +1615,10 @@ extern "C" int dspfft_zoomanim_execute(dspfft_zoomanim z, double xnum, double xd
 	// a finite scale at or below 1 / len (zero and negative included) is clamped to 1 / len by za_axis, as zoom.c:37-41 does
 	if (!(xden > 0) || !(yden > 0) || !std::isfinite(xnum / xden) || !std::isfinite(ynum / yden) || !std::isfinite(vx) || !std::isfinite(vy))
 		return fail(-1, "scales must be finite with positive denominators, offsets finite (the caller skips non-finite frames, zoom.c:342-345)");
-	if ((showsamples || layout == 1) && !dspfft_zoomanim_finish_launch)
-		return fail(-3, "zoom animation overlay / planar store: not in this build (the kernel is HIP-only, zoom_anim.hip)");
+	if ((showsamples || layout == 1 || z->trc) && !dspfft_zoomanim_finish_launch)
+		return fail(-3, "zoom animation overlay / planar store / transfer characteristic: not in this build (the kernel is HIP-only, zoom_anim.hip)");
 	const ZaOverlay ov = za_overlay(showsamples, xnum, xden, ynum, yden, vx, vy, z->vw, z->vh);
-	const bool finish = ov.mode || layout == 1;
+	const bool finish = ov.mode || layout == 1 || z->trc;
 	double wx, px, wy, py;
 	const int cw = za_axis(z->type, xnum, xden, z->w, vx, wx, px), ch = za_axis(z->type, ynum, yden, z->h, vy, wy, py);
 	if (!cw || !ch) return fail(-2, "centered basis: len * scale must exceed 1");
@@ -1627,8 +1632,15 @@ extern "C" int dspfft_zoomanim_execute(dspfft_zoomanim z, double xnum, double xd
 		return -4;
 	if (finish) {
 		char err[256] = "";
-		if (dspfft_zoomanim_finish_launch(d_out, X, &ov, layout, stream, err, sizeof err)) return fail(-4, "%s", err);
+		if (dspfft_zoomanim_finish_launch(d_out, X, &ov, layout, z->trc, stream, err, sizeof err)) return fail(-4, "%s", err);
 	}
+	return 0;
+}
+extern "C" int dspfft_zoomanim_set_trc(dspfft_zoomanim z, int trc)
+{
+	if (!z) return fail(-1, "null object");
+	if (trc && !trc_built(trc)) return fail(-1, "transfer characteristic %d is not built", trc);
+	z->trc = trc;
 	return 0;
 }
 extern "C" void dspfft_zoomanim_destroy(dspfft_zoomanim z)
@@ -2354,6 +2366,36 @@ extern "C" int dspfft_f32_to_u8(uint8_t *d, const float *src, double mul, uint64
 	return be_f32_to_u8(d, src, mul, len, s) ? fail(-4, "launch failed") : 0;
 }
 
+// ---- transfer characteristics (include/dspfft.h; trc_core.h; kernels in pointwise.hip and motion_ops.hip) ----
+extern "C" int dspfft_trc_from_name(const char *name) { return trc_from_name(name); }
+extern "C" const char *dspfft_trc_name(int trc) { return trc_name(trc); }
+extern "C" int dspfft_trc_apply_f32(float *d_dst, const float *d_src, uint64_t len, int trc, int inverse, void *stream)
+{
+	if (!d_dst || !d_src) return fail(-1, "transfer characteristic: null buffer");
+	if (!trc_built(trc)) return fail(-1, "transfer characteristic %d is not built", trc);
+	if (!dspfft_trc_apply_launch) return fail(-3, "transfer characteristic: not in this build (the kernel is HIP-only, pointwise.hip)");
+	if (!len) return 0;
+	return dspfft_trc_apply_launch(d_dst, d_src, len, trc, !!inverse, stream) ? fail(-4, "transfer characteristic: kernel launch failed") : 0;
+}
+namespace {
+int motion_linear(float *d_dst, const float *d_src, const int n[3], const int minbuf_hw[2], int store, double scalefactor, double normalization, int trc, void *stream)
+{
+	if (!d_dst || !d_src || !n || !minbuf_hw || n[0] < 1 || n[1] < 1 || n[2] < 1 || minbuf_hw[0] < n[1] || minbuf_hw[1] < n[2]) return fail(-1, "motion --linear: bad arguments");
+	if (!trc_built(trc)) return fail(-1, "motion --linear: transfer characteristic %d is not built", trc);
+	if (!dspfft_motion_linear_launch) return fail(-3, "motion --linear: not in this build (the kernels are HIP-only, motion_ops.hip)");
+	return dspfft_motion_linear_launch(d_dst, d_src, n, minbuf_hw, store, scalefactor, normalization, trc, stream) ? fail(-4, "motion --linear: kernel launch failed") : 0;
+}
+}  // namespace
+extern "C" int dspfft_motion_load_f32_linear(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], int trc, void *stream)
+{
+	return motion_linear(d_coeffs, d_pix, n, minbuf_hw, 0, 1.0, 1.0, trc, stream);
+}
+extern "C" int dspfft_motion_store_f32_linear(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], double scalefactor, double normalization,
+                                              int trc, void *stream)
+{
+	return motion_linear(d_pix, d_coeffs, n, minbuf_hw, 1, scalefactor, normalization, trc, stream);
+}
+
 // ---- scan's output frames (include/dspfft.h "scan's output frames on the device"; kernels in scan_frame.hip) ----
 struct dspfft_scanframes_s {
 	dspfft_scan_frame_opts o;
@@ -2363,6 +2405,7 @@ struct dspfft_scanframes_s {
 	uint32_t *flags;
 	uint32_t *saved;                        // the last current coordinate list (bottom-right marks to clear)
 	uint64_t saved_cap, saved_n;
+	int trc;                                // scan -g: the left-hand panels' transfer characteristic, 0 none
 	int prev;                               // what the last current mark lit: 0 nothing, 1 a range of prev_owner, 2 the saved list
 	uint32_t prev_lo, prev_hi;
 	const uint32_t *prev_owner;
@@ -2375,7 +2418,7 @@ SfOp sf_op(dspfft_scanframes sf, int op, void *stream)
 	o.op = op; o.w = sf->w; o.h = sf->h;
 	o.visualize = sf->o.visualize; o.spectrogram = sf->o.spectrogram; o.intermediates = sf->o.intermediates;
 	o.max_intermediates = sf->o.max_intermediates; o.parity_depth = sf->o.parity_depth;
-	o.scaletype = sf->o.spec_scaletype; o.signtype = sf->o.spec_signtype; o.gain = sf->o.spec_gain;
+	o.scaletype = sf->o.spec_scaletype; o.signtype = sf->o.spec_signtype; o.gain = sf->o.spec_gain; o.trc = sf->trc;
 	o.state = sf->state; o.partials = sf->partials; o.flags = sf->flags; o.stream = stream;
 	return o;
 }
@@ -2484,6 +2527,13 @@ extern "C" int dspfft_scanframes_compose(dspfft_scanframes sf, float *d_frame, f
 	SfOp o = sf_op(sf, SF_OP_COMPOSE, stream);
 	o.frame = d_frame; o.sum = d_sum; o.image = d_image; o.coeffs = d_coeffs; o.original = sf->o.parity_depth ? d_original : nullptr; o.frame_no = frame;
 	return sf_run(o);
+}
+extern "C" int dspfft_scanframes_set_trc(dspfft_scanframes sf, int trc)
+{
+	if (!sf) return fail(-1, "scan frames: bad arguments");
+	if (trc && !trc_built(trc)) return fail(-1, "scan frames: transfer characteristic %d is not built", trc);
+	sf->trc = trc;
+	return 0;
 }
 extern "C" int dspfft_scanframes_parity(dspfft_scanframes sf, uint64_t *first_frame, void *stream)
 {

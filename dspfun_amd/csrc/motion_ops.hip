@@ -2,6 +2,7 @@
 //   :617-640  pixel load with the inverse-spectrogram decodes (--ispec shift / flat / copy)
 //   :652-668  keep the N coefficients of largest magnitude (--coeff-limit): radix select, no full sort
 //   :755-776  output scaling (scalefactor, normalization), spectrogram encodes (--spec abs / shift / flat), clamp + lround
+//   :632-633, :768-769  --linear on float pixels: the transfer characteristic's decode on load, encode on store
 // Scalar math in double (`intermediate` of the reference's motion build, motion/Makefile:1-2).
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -12,6 +13,7 @@
 
 #include "../../include/dspfft.h"
 #include "motion_filter.h"
+#include "trc_core.h"
 
 static_assert(dspfft::MOTION_MODE_NONE == DSPFFT_MOTION_NONE && dspfft::MOTION_MODE_ABS == DSPFFT_MOTION_ABS && dspfft::MOTION_MODE_SHIFT == DSPFFT_MOTION_SHIFT &&
               dspfft::MOTION_MODE_FLAT == DSPFFT_MOTION_FLAT && dspfft::MOTION_MODE_COPY == DSPFFT_MOTION_COPY, "motion_filter.h's modes are dspfft.h's");
@@ -47,6 +49,29 @@ __global__ void motion_store_kernel(PIX *pix, const float *c, Reg r, int mode, d
 		const double pel = dspfft::motion_store_pel((double)c[o], mode, scalefactor, norm, cc);         // :759-771
 		if constexpr (sizeof(PIX) == 1) pix[o] = pel > 255 ? 255 : pel < 0 ? 0 : (uint8_t)lround(pel);  // :776
 		else pix[o] = (float)(pel / 255);                                                               // :774
+	}
+}
+
+// motion --linear with float pixels (--ispec / --spec none; copy stores alike).  The reference feeds the function a double, keeps the double
+// it returns and divides by 255 outside it, so these two use trc_core.h's exact evaluation (double, the device library's pow) and not the
+// production one, whose 1-ulp statement is about a float argument and a float result.
+__global__ void motion_linear_kernel(float *dst, const float *src, Reg r, int store, double scalefactor, double norm, int trc)
+{
+	TRC_NO_CONTRACT
+	const dspfft::TrcParams tp = dspfft::trc_params(trc);
+	const size_t total = (size_t)r.n[0] * r.n[1] * r.n[2];
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+		const size_t o = reg_off(r, i);
+		if (!store) {
+			double pel = (double)(src[o] * 255.0f);                                 // :623 float * int: a float product
+			pel = dspfft::trc_exact(tp, 1, pel / 255) * 255;                        // :633
+			dst[o] = (float)pel;                                                    // :637
+		} else {
+			double pel = (double)src[o] * scalefactor * norm;                       // :759
+			pel *= norm;                                                            // :767
+			pel = dspfft::trc_exact(tp, 0, pel / 255) * 255;                        // :769
+			dst[o] = (float)(pel / 255);                                            // :774
+		}
 	}
 }
 
@@ -140,6 +165,15 @@ extern "C" int dspfft_motion_store_f32(float *d_pix, const float *d_coeffs, cons
 	if (spec_mode < DSPFFT_MOTION_NONE || spec_mode > DSPFFT_MOTION_COPY) return mbad("spec mode: none, abs, shift, flat or copy");
 	Reg r; r.n[0] = n[0]; r.n[1] = n[1]; r.n[2] = n[2]; r.mh = minbuf_hw[0]; r.mw = minbuf_hw[1];
 	hipLaunchKernelGGL(motion_store_kernel<float>, dim3(mgrid((size_t)n[0] * n[1] * n[2])), dim3(256), 0, (hipStream_t)stream, d_pix, d_coeffs, r, spec_mode, scalefactor, normalization, c);
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+/* dspfft_motion_{load,store}_f32_linear's body (engine.cpp has checked the arguments and reaches this through a weak reference) */
+extern "C" __attribute__((visibility("hidden"))) int dspfft_motion_linear_launch(float *d_dst, const float *d_src, const int n[3], const int minbuf_hw[2], int store,
+                                                                                  double scalefactor, double normalization, int trc, void *stream)
+{
+	Reg r; r.n[0] = n[0]; r.n[1] = n[1]; r.n[2] = n[2]; r.mh = minbuf_hw[0]; r.mw = minbuf_hw[1];
+	hipLaunchKernelGGL(motion_linear_kernel, dim3(mgrid((size_t)n[0] * n[1] * n[2])), dim3(256), 0, (hipStream_t)stream, d_dst, d_src, r, store, scalefactor, normalization, trc);
 	return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -3,6 +3,7 @@
 //   spec/spec.c:81-139   coefficient -> spectrogram encoding (gain, range, log/linear scale, sign mapping)
 //   spec/ispec.c:84-151  the inverse decoding (without the separate sign-map image of :91-99)
 //   motion/motion.c:683-744  band-pass damp / boost, threshold, DC preservation, quantisation
+//   scan/scan.c:412-414, zoom/zoom.c:393-399  a transfer characteristic over a buffer (the decode of scan -g / zoom -g's input)
 // Scalar math follows the reference's `intermediate` = double.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -10,6 +11,7 @@
 
 #include "../../include/dspfft.h"
 #include "motion_filter.h"
+#include "trc_core.h"
 
 namespace {
 
@@ -126,6 +128,27 @@ __global__ void pruned_accumulate_kernel(float *sum, const float *coeffs, const 
 	}
 }
 
+// dst[i] = f(src[i]) with trc_core.h's production evaluation; dst == src allowed (a lane reads what it writes before it writes it).
+// [head, head + 4 nvec) goes in 16-byte accesses (the host found dst + head and src + head 16-byte aligned), the two ends one float a lane.
+__global__ void __launch_bounds__(256) trc_apply_kernel(float *dst, const float *src, uint64_t len, uint64_t head, uint64_t nvec, int trc, int inverse)
+{
+	const dspfft::TrcParams tp = dspfft::trc_params(trc);
+	const uint64_t tid = blockIdx.x * 256ull + threadIdx.x, stride = gridDim.x * 256ull;
+	const float4 *s4 = reinterpret_cast<const float4 *>(src + head);
+	float4 *d4 = reinterpret_cast<float4 *>(dst + head);
+	for (uint64_t i = tid; i < nvec; i += stride) {
+		float4 v = s4[i];
+		v.x = dspfft::trc_eval_f32(tp, inverse, v.x); v.y = dspfft::trc_eval_f32(tp, inverse, v.y);
+		v.z = dspfft::trc_eval_f32(tp, inverse, v.z); v.w = dspfft::trc_eval_f32(tp, inverse, v.w);
+		d4[i] = v;
+	}
+	const uint64_t tail = head + 4 * nvec, nends = head + (len - tail);
+	for (uint64_t i = tid; i < nends; i += stride) {
+		const uint64_t j = i < head ? i : tail + (i - head);
+		dst[j] = dspfft::trc_eval_f32(tp, inverse, src[j]);
+	}
+}
+
 thread_local char g_perr[256] = "";
 int bad(const char *m) { snprintf(g_perr, sizeof g_perr, "%s", m); return -1; }
 inline int grid_for(size_t n) { size_t b = (n + 255) / 256; return (int)(b < 1 ? 1 : b > 4096 ? 4096 : b); }
@@ -189,6 +212,22 @@ extern "C" int dspfft_motion_filter(float *d_coeffs, const int active[3], const 
 	const size_t total = (size_t)p.ad * p.ah * p.aw;
 	if (!total) return 0;
 	hipLaunchKernelGGL(motion_filter_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, d_coeffs, p, d_coeffs_coded);
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+/* dspfft_trc_apply_f32's body (engine.cpp has checked the arguments and reaches this through a weak reference) */
+extern "C" __attribute__((visibility("hidden"))) int dspfft_trc_apply_launch(float *d_dst, const float *d_src, uint64_t len, int trc, int inverse, void *stream)
+{
+	const uintptr_t a = (uintptr_t)d_dst, b = (uintptr_t)d_src;
+	uint64_t head = len, nvec = 0;
+	if ((a & 15) == (b & 15) && !(a & 3)) {
+		head = ((16 - (a & 15)) & 15) / 4;
+		if (head > len) head = len;
+		nvec = (len - head) / 4;
+	}
+	const uint64_t most = nvec > len - 4 * nvec ? nvec : len - 4 * nvec, groups = (most + 255) / 256;
+	hipLaunchKernelGGL(trc_apply_kernel, dim3((unsigned)(groups < 1 ? 1 : groups > 8192 ? 8192 : groups)), dim3(256), 0, (hipStream_t)stream,
+	                   d_dst, d_src, len, head, nvec, trc, inverse);
 	return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

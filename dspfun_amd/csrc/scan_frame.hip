@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "scan_frame_core.h"
+#include "trc_core.h"
 
 using namespace dspfft;
 
@@ -138,7 +139,10 @@ __global__ void __launch_bounds__(kThreads) sf_reduce_finish_kernel(const Extrem
 		}
 }
 
-// one lane per pixel: sum (+= image), the top-left and bottom-left panels, image back to -0, -P's comparison
+// one lane per pixel: sum (+= image), the top-left and bottom-left panels, image back to -0, -P's comparison.  TRC (scan -g): what goes
+// into the two panels is encoded (scan.c:412-414,455-457,486-488: only `pel`); the sum, -P and -M stay linear.  Without it the kernel is
+// the one it was: no extra arithmetic, the same stores.
+template <bool TRC>
 __global__ void __launch_bounds__(kThreads) sf_compose_kernel(SfOp o)
 {
 	SF_NO_CONTRACT
@@ -150,15 +154,19 @@ __global__ void __launch_bounds__(kThreads) sf_compose_kernel(SfOp o)
 		const uint32_t y = (uint32_t)(p / o.w), x = (uint32_t)(p - (uint64_t)y * o.w);
 		const uint64_t fw = (uint64_t)o.w * (1 + (o.visualize != 0)), fh = (uint64_t)o.h * (1 + (o.intermediates != 0));
 		float s[3], im[3];
+		TrcParams tp;
+		if (TRC) tp = trc_params(o.trc);
 		for (int z = 0; z < 3; z++) s[z] = o.sum[p * 3 + z];
 		if (o.image) {
 			for (int z = 0; z < 3; z++) { im[z] = o.image[p * 3 + z]; s[z] += im[z]; }
 			for (int z = 0; z < 3; z++) { o.sum[p * 3 + z] = s[z]; o.image[p * 3 + z] = kNegZero; }
 		}
-		for (int z = 0; z < 3; z++) o.frame[sf_frame_offset(fw, fh, x, y, z)] = s[z];
+		for (int z = 0; z < 3; z++) o.frame[sf_frame_offset(fw, fh, x, y, z)] = TRC ? trc_eval_f32(tp, 0, s[z]) : s[z];
 		if (o.intermediates && o.image)
-			for (int z = 0; z < 3; z++)
-				o.frame[sf_frame_offset(fw, fh, x, y + o.h, z)] = sf_intermediate(im[z], o.coeffs[z], o.state->mn[z], o.state->mx[z]);
+			for (int z = 0; z < 3; z++) {
+				const float v = sf_intermediate(im[z], o.coeffs[z], o.state->mn[z], o.state->mx[z]);
+				o.frame[sf_frame_offset(fw, fh, x, y + o.h, z)] = TRC ? trc_eval_f32(tp, 0, v) : v;
+			}
 		if (check)
 			for (int z = 0; z < 3; z++) differs |= sf_parity_differs(o.original[p * 3 + z], s[z], o.parity_depth);
 	}
@@ -234,7 +242,8 @@ extern "C" __attribute__((visibility("hidden"))) int dspfft_scanframes_launch(Sf
 			hipLaunchKernelGGL(sf_reduce_kernel, dim3(g), dim3(kThreads), 0, st, o->image, npix, (Extremes *)o->partials);
 			hipLaunchKernelGGL(sf_reduce_finish_kernel, dim3(1), dim3(kThreads), 0, st, (const Extremes *)o->partials, (int)g, o->coeffs, o->state);
 		}
-		hipLaunchKernelGGL(sf_compose_kernel, dim3(groups(npix)), dim3(kThreads), 0, st, *o);
+		if (o->trc) hipLaunchKernelGGL(sf_compose_kernel<true>, dim3(groups(npix)), dim3(kThreads), 0, st, *o);
+		else hipLaunchKernelGGL(sf_compose_kernel<false>, dim3(groups(npix)), dim3(kThreads), 0, st, *o);
 		if (o->original) hipLaunchKernelGGL(sf_parity_finish_kernel, dim3(1), dim3(kThreads), 0, st, o->state, (const uint32_t *)o->flags, groups(npix), o->frame_no);
 		break;
 	case SF_OP_PARITY:

@@ -127,6 +127,7 @@ struct SfOp {
 	int op;
 	uint32_t w, h;                          // image extent; the frame is w (1 + visualize) x h (1 + intermediates) per plane
 	int visualize, spectrogram, intermediates, max_intermediates, parity_depth, scaletype, signtype;
+	int trc;                                // COMPOSE: the transfer characteristic the left-hand panels are encoded with (trc_core.h), 0 none
 	double gain;                            // spectrogram gain before spec_create's float rounding
 	float *frame;
 	const float *coeffs, *original;

@@ -450,9 +450,10 @@ class FrameShardedZoom:
     Every frame is chirp-z (dspfft_zoomanim_*); a geometry the chirp-z plans do not cover raises (Zoom.animation keeps the dense product)."""
 
     def __init__(self, image_hwc, vw, vh, table, present, basis_type=0, vx=0.0, vy=0.0, xscale=(1.0, 1.0), yscale=(1.0, 1.0),
-                 showsamples=0, layout="rgb", group=None, lib=None):
+                 showsamples=0, layout="rgb", group=None, lib=None, trc=0):
         import ctypes as C
         from . import _lib
+        from .engine import trc_id
         from .zoom import resolve_frames, LAYOUTS
         self.lib = lib or _lib.load()
         self.G = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -470,6 +471,7 @@ class FrameShardedZoom:
         self.z = z
         self.work = torch.empty(self.lib.dspfft_zoomanim_work_floats(z), dtype=torch.float32, device=image_hwc.device)
         self._check(self.lib.dspfft_zoomanim_set_coeffs(z, self.coeffs.data_ptr(), self._st))
+        self._check(self.lib.dspfft_zoomanim_set_trc(z, trc_id(trc, self.lib)))      # zoom -g: every output sample encoded
 
     def _check(self, rc):
         if rc:

@@ -240,6 +240,69 @@ def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nbloc
         raise DspfftError(lib.dspfft_motion_last_error().decode())
 
 
+def trc_id(trc, lib=None):
+    """a transfer characteristic given by av_color_transfer_name's name or by its AVColorTransferCharacteristic id -> the id; 0 / None /
+    "none": no function.  Raises for one that is unknown or not built."""
+    lib = lib or _lib.load()
+    if trc is None or trc == 0 or trc == "none":
+        return 0
+    v = lib.dspfft_trc_from_name(trc.encode()) if isinstance(trc, str) else (int(trc) if lib.dspfft_trc_name(int(trc)) else -1)
+    if v < 0:
+        raise DspfftError(f"transfer characteristic {trc!r} is unknown or not built")
+    return v
+
+
+def trc_apply(t, trc, inverse=False, out=None, stream=None, lib=None):
+    """dspfft_trc_apply_f32 over a contiguous float32 device tensor: encode (linear light -> coded), or decode with inverse=True (the
+    input side of scan -g / zoom -g).  out: a tensor of the same size (t itself for in place); a new one by default."""
+    lib = lib or _lib.load()
+    trc = trc_id(trc, lib)
+    if out is None:
+        out = t.new_empty(t.shape)
+    assert t.is_contiguous() and out.is_contiguous() and t.numel() == out.numel() and t.element_size() == 4 and out.element_size() == 4
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    if trc == 0:
+        if out.data_ptr() != t.data_ptr():
+            out.copy_(t)
+        return out
+    if lib.dspfft_trc_apply_f32(C.c_void_p(out.data_ptr()), C.c_void_p(t.data_ptr()), t.numel(), trc, int(bool(inverse)), C.c_void_p(stream)):
+        raise DspfftError(lib.dspfft_last_error().decode())
+    return out
+
+
+_MOTION_MODES = {"none": 0, "abs": 1, "shift": 2, "flat": 3, "copy": 4}
+
+
+def _motion_linear(fn, mode, allowed, d_dst, d_src, n, minbuf_hw, extra, trc, stream, lib):
+    lib = lib or _lib.load()
+    mode = _MOTION_MODES[mode] if isinstance(mode, str) else int(mode)
+    if mode not in allowed:
+        return -1                                             # motion.c:631-633,765-769: --linear acts in these cases of the switch only
+    hw = (n[1], n[2]) if minbuf_hw is None else minbuf_hw
+    rc = getattr(lib, fn)(_ptr(d_dst), _ptr(d_src), _ia(n), _ia(hw), *extra, trc_id(trc, lib), C.c_void_p(stream))
+    if rc not in (0, -1):
+        raise DspfftError(lib.dspfft_last_error().decode())
+    return rc
+
+
+def motion_load_f32_linear(d_coeffs, d_pix, n, minbuf_hw=None, trc="iec61966-2-1", ispec_mode="none", stream=0, lib=None):
+    """dspfft_motion_load_f32_linear (motion --linear on float pixels, motion.c:623,633).  Returns 0; -1, decided here before the
+    library is called and with nothing written, for an ispec_mode other than none (the reference decodes a spectrogram instead); -1 from
+    the library for trc 0 (no function).  A trc name or id that is unknown or not built raises DspfftError (trc_id), as does a failed launch."""
+    return _motion_linear("dspfft_motion_load_f32_linear", ispec_mode, (0,), d_coeffs, d_pix, n, minbuf_hw, (), trc, stream, lib)
+
+
+def motion_store_f32_linear(d_pix, d_coeffs, n, minbuf_hw=None, scalefactor=1.0, normalization=1.0, trc="iec61966-2-1", spec_mode="none",
+                            stream=0, lib=None):
+    """dspfft_motion_store_f32_linear (motion.c:759,767-769,774).  Returns 0; -1, decided here before the library is called and with
+    nothing written, for a spec_mode other than none / copy; -1 from the library for trc 0.  A trc that is unknown or not built raises
+    DspfftError (trc_id), as does a failed launch."""
+    return _motion_linear("dspfft_motion_store_f32_linear", spec_mode, (0, 4), d_pix, d_coeffs, n, minbuf_hw,
+                          (float(scalefactor), float(normalization)), trc, stream, lib)
+
+
 SPEC_SCALES = {"none": 0, "linear": 1, "log": 2}
 SPEC_SIGNS = {"none": 0, "abs": 1, "shift": 2, "saturate": 3}
 
@@ -248,10 +311,11 @@ class ScanFrames:
     """dspfft_scanframes: scan's output frames composed on the device (scan/scan.c:366-536).  Takes torch device tensors (float32 HWC
     images, uint32 owner / coordinate tables, the float32 frame of frame_floats elements); every failure raises DspfftError.
     Options as scan's: visualize (-v), spectrogram (-s, implies -v), intermediates (-i), max_intermediates (-M, implies -i),
-    spec_gain (--spec-gain, 0: the default), spec_scale / spec_sign (--spec-opts scale= / sign=), parity_depth (-P: 8, 16 or 32)."""
+    spec_gain (--spec-gain, 0: the default), spec_scale / spec_sign (--spec-opts scale= / sign=), parity_depth (-P: 8, 16 or 32),
+    trc (-g: the transfer characteristic, a name or an id, the left-hand panels are encoded with; 0: none)."""
 
     def __init__(self, w, h, visualize=False, spectrogram=False, intermediates=False, max_intermediates=False, spec_gain=0.0,
-                 spec_scale="none", spec_sign="none", parity_depth=0, lib=None):
+                 spec_scale="none", spec_sign="none", parity_depth=0, lib=None, trc=0):
         self._lib = lib or _lib.load()
         self._h = None
         o = _lib.ScanFrameOpts(int(bool(visualize)), int(bool(spectrogram)), int(bool(intermediates)), int(bool(max_intermediates)), float(spec_gain),
@@ -263,6 +327,11 @@ class ScanFrames:
         self.w, self.h = int(w), int(h)
         self.visualize = bool(visualize or spectrogram)
         self.intermediates = bool(intermediates or max_intermediates)
+        if trc:
+            self.set_trc(trc)
+
+    def set_trc(self, trc):
+        self._check(self._lib.dspfft_scanframes_set_trc(self._h, trc_id(trc, self._lib)))
 
     @property
     def shape(self):

@@ -4,7 +4,7 @@ import ctypes as C
 import math
 
 from . import _lib
-from .engine import Plan, DspfftError, REDFT10
+from .engine import Plan, DspfftError, REDFT10, trc_apply, trc_id
 
 INTERPOLATED, CENTERED, NATIVE = 0, 1, 2     # zoom/zoom.c:20-26
 CACHE_PLANS = 4       # frame plans kept per path: an animated zoom (a new scale every frame) would otherwise keep a plan and a frame-sized work
@@ -116,9 +116,10 @@ class Zoom:
             raise DspfftError(self.lib.dspfft_zoom_last_error().decode())
         return b, nc
 
-    def animation(self, vw, vh, basis_type=INTERPOLATED):
-        """a ZoomAnimation over these coefficients: per-frame scale and offset without re-planning"""
-        return ZoomAnimation(self, vw, vh, basis_type)
+    def animation(self, vw, vh, basis_type=INTERPOLATED, trc=0):
+        """a ZoomAnimation over these coefficients: per-frame scale and offset without re-planning; trc (a name or an id, zoom -g):
+        the transfer characteristic every output sample is encoded with"""
+        return ZoomAnimation(self, vw, vh, basis_type, trc)
 
     def frame(self, vw, vh, xscale=(1.0, 1.0), yscale=(1.0, 1.0), vx=0.0, vy=0.0, basis_type=INTERPOLATED, method="auto"):
         """one output frame: (vh, vw, 3) f32.  method "auto": fast transforms on the DCT-III grid (dspfft_zoomfft_*) when the scaled lengths
@@ -185,9 +186,9 @@ class ZoomAnimation:
     the listed convolutions), every frame takes the dense product (Zoom.frame(method="gemm")), which has no --showsamples overlay.
     The coefficients are transposed once, here: call refresh() after changing zoom.coeffs in place."""
 
-    def __init__(self, zoom, vw, vh, basis_type=INTERPOLATED):
+    def __init__(self, zoom, vw, vh, basis_type=INTERPOLATED, trc=0):
         self.zoom, self.lib, self.torch = zoom, zoom.lib, zoom.torch
-        self.vw, self.vh, self.basis_type = vw, vh, basis_type
+        self.vw, self.vh, self.basis_type, self.trc = vw, vh, basis_type, 0
         z = C.c_void_p()
         rc = self.lib.dspfft_zoomanim_create(C.byref(z), zoom.w, zoom.h, basis_type, vw, vh)
         if rc not in (0, -2):
@@ -196,6 +197,14 @@ class ZoomAnimation:
         if self.z is not None:
             self.work = self.torch.empty(self.lib.dspfft_zoomanim_work_floats(self.z), dtype=self.torch.float32, device=zoom.coeffs.device)
             self.refresh()
+        self.set_trc(trc)
+
+    def set_trc(self, trc):
+        """zoom -g: encode every output sample (after the overlay) with this transfer characteristic, a name or an id; 0: none"""
+        trc = trc_id(trc, self.lib)
+        if self.z is not None and (trc or self.trc) and self.lib.dspfft_zoomanim_set_trc(self.z, trc):      # (0 on an object never told: no call)
+            raise DspfftError(self.lib.dspfft_zoomanim_last_error().decode())
+        self.trc = trc
 
     def refresh(self):
         if self.z is not None and self.lib.dspfft_zoomanim_set_coeffs(self.z, self.zoom.coeffs.data_ptr(), self.torch.cuda.current_stream().cuda_stream):
@@ -210,6 +219,8 @@ class ZoomAnimation:
                 raise DspfftError("--showsamples is not built for the dense product (the chirp-z plans do not cover this geometry)")
             f = self.zoom.frame(self.vw, self.vh, xscale, yscale, vx, vy, self.basis_type, method="gemm")
             f = f if lay == 0 else f.permute(2, 0, 1)[[1, 2, 0]].contiguous()
+            if self.trc:
+                trc_apply(f, self.trc, out=f, lib=self.lib)
             if out is not None:
                 out.copy_(f)
                 return out

@@ -23,6 +23,10 @@
  *   -P / --measure-parity (scan.c:41-76,176-215, -s implies -v, -M implies -i): the output frames of scan.c:366-536 composed on the device
  *     (include/dspfft.h "scan's output frames"); a frame for EVERY i in [offset, offset + nframes), past the limit included.  -P prints
  *     the reference's message (depth 8 for P6 input, 32 for PF).  -g / --linear is refused (needs a colourspace transform).
+ *   --trc NAME (av_color_transfer_name's names: iec61966-2-1, bt709, gamma22, ...; include/dspfft.h lists what is built): the work -g does
+ *     once the colourspace is known.  The input's pixels are NAME-coded: they are decoded on the device before the forward transform (and
+ *     before -P's copy of the original, scan.c:268-287), every frame's left-hand panels are encoded with NAME (scan.c:412-414,455-457,
+ *     486-488), and so is the final image.
  *   --video PATH: every frame as raw gbrpf32le, concatenated (ffmpeg -f rawvideo -pix_fmt gbrpf32le -s W'xH' -r 20 -i PATH); the
  *     geometry goes to stderr.  Frames come down asynchronously into two pinned buffers: frame k - 1 is written while frame k computes
  *     and copies.
@@ -85,7 +89,7 @@ int main(int argc, char *argv[])
 	size_t offset = 0, nframes = 0;
 	dspfft_scan_frame_opts fo;
 	memset(&fo, 0, sizeof fo);
-	int parity = 0;
+	int parity = 0, trc = 0;
 	const char *video = NULL;
 	for (int a = 1; a < argc; a++) {
 		const char *s = argv[a];
@@ -95,8 +99,12 @@ int main(int argc, char *argv[])
 		else if (!strcmp(s, "-M") || !strcmp(s, "--max-intermediates")) fo.intermediates = fo.max_intermediates = 1;
 		else if (!strcmp(s, "-P") || !strcmp(s, "--measure-parity")) parity = 1;
 		else if (!strcmp(s, "-g") || !strcmp(s, "--linear")) {
-			fprintf(stderr, "--linear is not supported: it needs ImageMagick's colourspace transform and libavutil's transfer function\n");
+			fprintf(stderr, "--linear is not supported: it needs ImageMagick's colourspace transform and libavutil's transfer function"
+			        " (when the file is known to be sRGB-coded: --trc iec61966-2-1)\n");
 			return 2;
+		} else if (!strcmp(s, "--trc") && a + 1 < argc) {
+			trc = dspfft_trc_from_name(argv[++a]);
+			if (trc < 0) { fprintf(stderr, "--trc %s: unknown transfer characteristic, or not built\n", argv[a]); return 2; }
 		} else if (!strcmp(s, "--spec-gain") && a + 1 < argc) fo.spec_gain = strtod(argv[++a], NULL);        /* precision_strtoi, INTERMEDIATE=D */
 		else if (!strcmp(s, "--spec-opts") && a + 1 < argc) {
 			const char *e = parse_spec_opts(argv[++a], &fo.spec_scaletype, &fo.spec_signtype);
@@ -113,7 +121,8 @@ int main(int argc, char *argv[])
 	}
 	if (npos < 2) {
 		fprintf(stderr, "usage: %s <in> <out.pf> [step] [method] [--offset N] [--skip] [--invert] [--frames N] [-v] [-s] [--spec-gain G] "
-		        "[--spec-opts k=v:...] [-i] [-M] [-P] [--video PATH]\n", argv[0]);
+		        "[--spec-opts k=v:...] [-i] [-M] [-P] [--video PATH] [--trc NAME]\n"
+		        "  --trc NAME: the input is NAME-coded (iec61966-2-1, bt709, gamma22, ...): decoded before the transform, frames and output encoded\n", argv[0]);
 		return 2;
 	}
 	size_t width, height;
@@ -130,6 +139,12 @@ int main(int argc, char *argv[])
 	HIP(hipMalloc((void **)&d_coeffs, n * 4)); HIP(hipMalloc((void **)&d_sum, n * 4)); HIP(hipMalloc((void **)&d_work, n * 4));
 	HIP(hipMalloc((void **)&d_ids, npix * 4));
 	HIP(hipMemcpy(d_coeffs, pix, n * 4, hipMemcpyHostToDevice));
+	float *d_orig = NULL;
+	if (trc) DSP(dspfft_trc_apply_f32(d_coeffs, d_coeffs, n, trc, 1, NULL));                              /* to linear light */
+	if (parity) {                                                                                         /* scan.c:283-287 */
+		HIP(hipMalloc((void **)&d_orig, n * 4));
+		HIP(hipMemcpy(d_orig, d_coeffs, n * 4, hipMemcpyDeviceToDevice));
+	}
 
 	dspfft_plan fwd, inv;
 	const int dims[2] = {(int)height, (int)width}, k10[2] = {DSPFFT_REDFT10, DSPFFT_REDFT10}, k01[2] = {DSPFFT_REDFT01, DSPFFT_REDFT01};
@@ -188,7 +203,7 @@ int main(int argc, char *argv[])
 	const int fill = !skip && offset > 0;
 	/* ---- the output frames (scan.c:366-536) ---- */
 	dspfft_scanframes sf = NULL;
-	float *d_frame = NULL, *d_image = NULL, *d_orig = NULL, *h_frame[2] = {NULL, NULL};
+	float *d_frame = NULL, *d_image = NULL, *h_frame[2] = {NULL, NULL};
 	uint32_t *d_mark = NULL;                /* owner index with DC keeping its index (the marks); NULL: coordinate lists */
 	FILE *vf = NULL;
 	size_t ffloats = 0;
@@ -200,15 +215,12 @@ int main(int argc, char *argv[])
 		fclose(f);
 		fo.parity_depth = parity ? (!strcmp(magic, "P6") ? 8 : 32) : 0;                           /* host/rawio.h: P6 8-bit, PF float */
 		DSP(dspfft_scanframes_create(&sf, w, h, &fo));
+		if (trc) DSP(dspfft_scanframes_set_trc(sf, trc));
 		ffloats = dspfft_scanframes_frame_floats(sf);
 		HIP(hipMalloc((void **)&d_frame, ffloats * 4));
 		if (fo.intermediates) {
 			HIP(hipMalloc((void **)&d_image, n * 4));
 			HIP(hipMemsetD32((hipDeviceptr_t)d_image, 0x80000000u, n));                           /* -0.0f: the step adds into it */
-		}
-		if (parity) {
-			HIP(hipMalloc((void **)&d_orig, n * 4));
-			HIP(hipMemcpy(d_orig, pix, n * 4, hipMemcpyHostToDevice));
 		}
 		if (fo.visualize && !per_frame_lists) {
 			HIP(hipMalloc((void **)&d_mark, npix * 4));
@@ -304,6 +316,7 @@ int main(int argc, char *argv[])
 	}
 	#undef STAMP
 	float *sum = malloc(n * 4);
+	if (trc) DSP(dspfft_trc_apply_f32(d_sum, d_sum, n, trc, 0, NULL));                                    /* the output is coded as the input was */
 	HIP(hipMemcpy(sum, d_sum, n * 4, hipMemcpyDeviceToHost));
 	double err = 0;
 	for (size_t j = 0; j < n; j++) { const double e = fabs((double)sum[j] - pix[j]); if (e > err) err = e; }

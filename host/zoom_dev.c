@@ -4,14 +4,17 @@
  * frame store on the device.  The option arithmetic before the loop (zoom.c:268-303) is zoom_args.c's.
  *
  *   zoom_dev [-s <scale>] [-r WxH] [-p XxY] [-v WxH] [-c] [-P] [-%] [--basis interpolated|centered|native] [--showsamples[=point|grid]]
- *            [-n N] [-q] [--params FILE] [--video PATH] <input.ppm|.pf> <output.pf>
+ *            [-n N] [-q] [--params FILE] [--video PATH] [--trc NAME] <input.ppm|.pf> <output.pf>
  *
  * -s takes a decimal or num/den, or XxY of those, as zoom does.  The per-frame expressions (-x, -y, -S, -X, -Y) need libavutil's evaluator
  * and are refused: --params FILE gives, per line d, the values x y S X Y those expressions would produce at frame d, "-" for one that was
  * not given (a column is all numbers or all "-"; nan and inf are numbers).  They are applied in zoom.c:321-345's order: S sets both scales
  * to (value, 1), X and Y then override one axis each, x and y set the position; the state persists across frames where a column is "-",
  * and a frame with a non-finite position or scale is skipped with the reference's message.  Without --params every frame is the first.
- * -g (linear RGB) needs ImageMagick's and libavutil's transfer functions and is refused.
+ * -g (linear RGB) asks ImageMagick for the file's colourspace, which a PF / P6 reader cannot answer, and is refused.  --trc NAME
+ * (av_color_transfer_name's names: iec61966-2-1, bt709, gamma22, ...; include/dspfft.h lists what is built) does the work -g does once the
+ * colourspace is known: the input's pixels are NAME-coded and are decoded on the device before the forward transform; every frame of
+ * --video and the final image are encoded with NAME after the overlay (zoom.c:377-399).  Not built for the dense product.
  *
  * output.pf: the last frame, "PF\nVW VH\n-1.0\n" + VH x VW x 3 little-endian f32, top row first (host/rawio.h).
  * --video PATH: every frame as raw gbrpf32le, concatenated (ffmpeg -f rawvideo -pix_fmt gbrpf32le -s VWxVH -r 60 -i PATH; 60 is zoom's
@@ -36,7 +39,8 @@
 static int usage(const char *self)
 {
 	fprintf(stderr, "usage: %s [-s scale] [-r WxH] [-p XxY] [-v WxH] [-c] [-P] [-%%] [--basis interpolated|centered|native] "
-	        "[--showsamples[=point|grid]] [-n N] [-q] [--params FILE] [--video PATH] <input> <output.pf>\n", self);
+	        "[--showsamples[=point|grid]] [-n N] [-q] [--params FILE] [--video PATH] [--trc NAME] <input> <output.pf>\n"
+	        "  --trc NAME: the input is NAME-coded (iec61966-2-1, bt709, gamma22, ...): decoded before the transform, every frame encoded\n", self);
 	return 2;
 }
 
@@ -79,10 +83,10 @@ int main(int argc, char *argv[])
 	long double vx = 0, vy = 0, xnum = 1, ynum = 1, lw = 0, lh = 0;
 	unsigned long long xden = 1, yden = 1;
 	size_t vw = 0, vh = 0, nframes = 1;
-	int centered = 0, input_coords = 0, pct = 0, quiet = 0, showsamples = 0, basis = 0;
+	int centered = 0, input_coords = 0, pct = 0, quiet = 0, showsamples = 0, basis = 0, trc = 0;
 	const char *params = NULL, *video = NULL;
 	const struct option opts[] = {{"showsamples", optional_argument, NULL, 1}, {"basis", required_argument, NULL, 2},
-	                              {"params", required_argument, NULL, 3}, {"video", required_argument, NULL, 4}, {0}};
+	                              {"params", required_argument, NULL, 3}, {"video", required_argument, NULL, 4}, {"trc", required_argument, NULL, 5}, {0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:r:p:v:cP%n:qgx:y:S:X:Y:", opts, NULL)) != -1) {
 		switch (c) {
@@ -102,7 +106,10 @@ int main(int argc, char *argv[])
 		case '%': pct = 1; break;
 		case 'n': nframes = strtoull(optarg, NULL, 10); break;
 		case 'q': quiet = 1; break;
-		case 'g': fprintf(stderr, "-g (linear RGB) is not supported: it needs ImageMagick's and libavutil's transfer functions\n"); return 2;
+		case 'g':
+			fprintf(stderr, "-g (linear RGB) is not supported: it needs ImageMagick's and libavutil's transfer functions"
+			        " (when the file is known to be sRGB-coded: --trc iec61966-2-1)\n");
+			return 2;
 		case 'x': case 'y': case 'S': case 'X': case 'Y':
 			fprintf(stderr, "-%c: expressions are not evaluated here; give their per-frame values with --params FILE\n", c); return 2;
 		case 1:
@@ -117,6 +124,10 @@ int main(int argc, char *argv[])
 			break;
 		case 3: params = optarg; break;
 		case 4: video = optarg; break;
+		case 5:
+			trc = dspfft_trc_from_name(optarg);
+			if (trc < 0) { fprintf(stderr, "--trc %s: unknown transfer characteristic, or not built\n", optarg); return 2; }
+			break;
 		default: return usage(argv[0]);
 		}
 	}
@@ -139,6 +150,7 @@ int main(int argc, char *argv[])
 	HIP(hipMalloc((void **)&d_coeffs, sizeof(float) * n3));
 	HIP(hipMalloc((void **)&d_frame, sizeof(float) * npix * 3));
 	HIP(hipMemcpy(d_coeffs, pix, sizeof(float) * n3, hipMemcpyHostToDevice));
+	if (trc && dspfft_trc_apply_f32(d_coeffs, d_coeffs, n3, trc, 1, NULL)) { fprintf(stderr, "--trc: %s\n", dspfft_last_error()); return 1; }   /* to linear light */
 	dspfft_plan fwd;
 	if (dspfft_plan_many_r2r(&fwd, 2, (int[]){(int)height, (int)width}, 3, NULL, 3, 1, NULL, 3, 1, (int[]){DSPFFT_REDFT10, DSPFFT_REDFT10}) ||
 	    dspfft_execute(fwd, d_coeffs, d_coeffs, NULL)) { fprintf(stderr, "forward transform: %s\n", dspfft_last_error()); return 1; }
@@ -148,8 +160,9 @@ int main(int argc, char *argv[])
 	float *xb = NULL, *yb = NULL;
 	if (rc == 0) {
 		HIP(hipMalloc((void **)&d_work, sizeof(float) * dspfft_zoomanim_work_floats(z)));
-		if (dspfft_zoomanim_set_coeffs(z, d_coeffs, NULL)) { fprintf(stderr, "zoomanim: %s\n", dspfft_zoomanim_last_error()); return 1; }
+		if (dspfft_zoomanim_set_coeffs(z, d_coeffs, NULL) || dspfft_zoomanim_set_trc(z, trc)) { fprintf(stderr, "zoomanim: %s\n", dspfft_zoomanim_last_error()); return 1; }
 	} else if (rc == -2) {
+		if (trc) { fprintf(stderr, "--trc: not built for the dense product (%s)\n", dspfft_zoomanim_last_error()); return 1; }
 		if (showsamples) { fprintf(stderr, "--showsamples: not built for the dense product (%s)\n", dspfft_zoomanim_last_error()); return 1; }
 		HIP(hipMalloc((void **)&xb, sizeof(float) * vw * width));
 		HIP(hipMalloc((void **)&yb, sizeof(float) * vh * height));

@@ -415,6 +415,24 @@ int dspfft_scanframes_compose(dspfft_scanframes sf, float *d_frame, float *d_sum
 int dspfft_scanframes_parity(dspfft_scanframes sf, uint64_t *first_frame, void *hip_stream);
 void dspfft_scanframes_destroy(dspfft_scanframes sf);
 
+/* ---- transfer characteristics: scan -g, zoom -g, motion --linear (scan.c:412-414,455-457,486-488, zoom.c:393-399, motion.c:632-633,
+ * 768-769) ----
+ * The reference takes the functions from libavutil (av_csp_trc_func_from_id and its inverse); the table in dspfun_amd/csrc/trc_core.h is
+ * written from the standards and from recollection of libavutil's csp.c (parity unpinned).  Ids are AVColorTransferCharacteristic's, names
+ * av_color_transfer_name's.  Built: the ids below; log100, log316, bt1361e, smpte2084, smpte428 and arib-std-b67 are refused.
+ * The frame kernels and dspfft_trc_apply_f32 evaluate float -> float within 1 float ulp of the double evaluation rounded to float, bit-equal
+ * where that is +-0, NaN or +-inf; motion's load and store evaluate in double as the reference does. */
+enum { DSPFFT_TRC_NONE = 0, DSPFFT_TRC_BT709 = 1, DSPFFT_TRC_GAMMA22 = 4, DSPFFT_TRC_GAMMA28 = 5, DSPFFT_TRC_SMPTE170M = 6,
+       DSPFFT_TRC_SMPTE240M = 7, DSPFFT_TRC_LINEAR = 8, DSPFFT_TRC_IEC61966_2_4 = 11, DSPFFT_TRC_IEC61966_2_1 = 13,
+       DSPFFT_TRC_BT2020_10 = 14, DSPFFT_TRC_BT2020_12 = 15 };
+int dspfft_trc_from_name(const char *name);                 /* id, or -1: unknown or not built */
+const char *dspfft_trc_name(int trc);                       /* NULL when not built */
+/* d_dst[i] = inverse ? decode(d_src[i]) : encode(d_src[i]); d_dst == d_src allowed; the input side of scan -g / zoom -g.  HIP-only. */
+int dspfft_trc_apply_f32(float *d_dst, const float *d_src, uint64_t len, int trc, int inverse, void *hip_stream);
+/* scan -g: compose encodes what it stores into the top-left and bottom-left panels (scan.c:412-414,455-457,486-488); d_sum, -P and -M
+ * stay on linear values, the right-hand panels are never encoded.  0 (the default): frames as without the call, byte for byte. */
+int dspfft_scanframes_set_trc(dspfft_scanframes sf, int trc);
+
 /* ---- the rest of motion's block loop (motion/motion.c), HIP-only entry points ---- */
 enum { DSPFFT_MOTION_NONE = 0, DSPFFT_MOTION_ABS = 1, DSPFFT_MOTION_SHIFT = 2, DSPFFT_MOTION_FLAT = 3, DSPFFT_MOTION_COPY = 4 };
 /* motion.c:617-640: the {n[0],n[1],n[2]} corner of an 8-bit buffer -> float, both laid out as planes of minbuf_hw[0] x minbuf_hw[1];
@@ -429,6 +447,13 @@ int dspfft_motion_store_u8(uint8_t *d_pix, const float *d_coeffs, const int n[3]
 int dspfft_motion_load_f32(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], int ispec_mode, double ic, double normalization, void *hip_stream);
 int dspfft_motion_store_f32(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], int spec_mode,
                             double scalefactor, double normalization, double c, void *hip_stream);
+/* the float-pixel pair with motion --linear, which the reference applies with --ispec / --spec none (and copy on the store) only:
+ * load  pel = sample * 255 (a float product); coeff = (float)(decode(pel / 255) * 255)          (motion.c:623,633)
+ * store pel = coeff * scalefactor * normalization; pel *= normalization; sample = (float)(encode(pel / 255) * 255 / 255)   (:759,767-769,774)
+ * in double with the exact evaluation.  -1 for a trc that is 0 or not built. */
+int dspfft_motion_load_f32_linear(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], int trc, void *hip_stream);
+int dspfft_motion_store_f32_linear(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2],
+                                   double scalefactor, double normalization, int trc, void *hip_stream);
 /* motion.c:756-788 with -d / --dither (spec none, 8-bit pixels, !linear): the 8-bit store with 2-D Floyd-Steinberg error diffusion, plane
  * by plane (the z planes of a block are independent, and so are blocks).  Per pixel, in raster order: pel = c * scalefactor * normalization,
  * pel *= normalization, byte = clamp + lround, dp = c - byte / (normalization^2 scalefactor), and dp * 7/16, 3/16, 5/16, 1/16 go into the
@@ -542,6 +567,10 @@ int dspfft_zoomanim_execute(dspfft_zoomanim z, double xnum, double xden, double 
                             int showsamples, int layout, float *d_out, float *d_work, void *hip_stream);
 void dspfft_zoomanim_destroy(dspfft_zoomanim z);
 const char *dspfft_zoomanim_last_error(void);
+/* zoom -g: every output sample is encoded after the overlay (zoom.c:377-399; the green marker goes through it like any sample), in place
+ * on the interleaved frame and inside the planar store.  0 (the default): launches and bytes as without the call.  A trc other than 0
+ * makes dspfft_zoomanim_execute return -3 in a build without the kernels. */
+int dspfft_zoomanim_set_trc(dspfft_zoomanim z, int trc);
 
 /* ---- applybasis' basis x pixel partial sums on the matrix cores ----
  * applybasis/applybasis.c:410-431, forward direction:
