@@ -17,6 +17,7 @@ SYMBOLS = [
     "dspfft_plan_many_r2r", "dspfft_plan_r2r_2d", "dspfft_plan_set_scale", "dspfft_plan_set_axis_scale0",
     "dspfft_plan_many_r2r_f64", "dspfft_plan_set_scale_f64", "dspfft_plan_set_axis_scale0_f64", "dspfft_execute_f64", "dspfft_execute_masked_accumulate_f64", "dspfft_plan_scan_prepare", "dspfft_plan_set_input_window", "dspfft_plan_set_output_alternate", "dspfft_set_plan_effort", "dspfft_get_plan_effort",
     "dspfft_plan_many_r2r_ordered", "dspfft_plan_guru_r2r", "dspfft_execute_roundtrip", "dspfft_execute_roundtrip_u8", "dspfft_execute_roundtrip_u8_dither",
+    "dspfft_roundtrip_topn_work_bytes", "dspfft_execute_roundtrip_topn", "dspfft_execute_roundtrip_u8_topn", "dspfft_motion_topn_blocks_work_bytes", "dspfft_motion_topn_blocks",
     "dspfft_execute", "dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
     "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_execute_n", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
     "dspfft_last_error", "dspfft_version", "dspfft_set_thread_plan_effort", "dspfft_get_thread_plan_effort", "dspfft_fftw_sparse_uploads",
@@ -113,6 +114,11 @@ def bind(lib):
     lib.dspfft_execute_roundtrip.argtypes = [vp, vp, vp, vp, C.POINTER(MotionFilterParams), vp, vp]
     lib.dspfft_execute_roundtrip_u8.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), vp, vp]
     lib.dspfft_execute_roundtrip_u8_dither.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.POINTER(MotionFilterParams), vp, vp]
+    if hasattr(lib, "dspfft_execute_roundtrip_topn"):     # (absent from a build of an earlier commit named by DSPFFT_LIB_PATH for an A/B run)
+        lib.dspfft_roundtrip_topn_work_bytes.restype = C.c_size_t
+        lib.dspfft_roundtrip_topn_work_bytes.argtypes = [vp, vp]
+        lib.dspfft_execute_roundtrip_topn.argtypes = [vp, vp, vp, vp, C.POINTER(MotionFilterParams), C.c_size_t, vp, C.c_size_t, vp, vp]
+        lib.dspfft_execute_roundtrip_u8_topn.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.c_size_t, vp, C.c_size_t, vp, vp]
     lib.dspfft_plan_set_scale_f64.argtypes = [vp, C.c_double]
     lib.dspfft_plan_set_axis_scale0_f64.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     lib.dspfft_execute_f64.argtypes = [vp, vp, vp, vp]
@@ -206,6 +212,10 @@ def bind(lib):
         lib.dspfft_motion_topn_work_bytes.restype = C.c_size_t
         lib.dspfft_motion_topn_work_bytes.argtypes = [C.c_size_t]
         lib.dspfft_motion_topn.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]
+        if hasattr(lib, "dspfft_motion_topn_blocks"):
+            lib.dspfft_motion_topn_blocks_work_bytes.restype = C.c_size_t
+            lib.dspfft_motion_topn_blocks_work_bytes.argtypes = [C.c_size_t, C.c_size_t]
+            lib.dspfft_motion_topn_blocks.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_longlong, C.c_size_t, vp, C.c_size_t, vp]
         lib.dspfft_motion_last_error.restype = C.c_char_p
         lib.dspfft_motion_dither_u8.argtypes = [vp, vp, C.POINTER(DitherGeom), C.c_double, C.c_double, vp]
         lib.dspfft_scan_pruned_accumulate.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]

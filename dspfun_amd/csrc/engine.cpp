@@ -27,6 +27,7 @@
 #include "scan_frame_core.h"
 #include "zoom_anim_core.h"
 #include "trc_core.h"
+#include "topn_core.h"
 
 using namespace dspfft;
 
@@ -44,6 +45,13 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_zoomanim_finis
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_trc_apply_launch(float *d_dst, const float *d_src, uint64_t len, int trc, int inverse, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_motion_linear_launch(float *d_dst, const float *d_src, const int n[3], const int minbuf_hw[2], int store,
                                                                                         double scalefactor, double normalization, int trc, void *stream);
+
+// block_topn.hip's and motion_ops.hip's launchers behind dspfft_execute_roundtrip_topn / _u8_topn.  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_topn_launch(const dspfft::BlockRtTopnArgs *a, int nwg, size_t lds, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_topn_blocks_launch(float *d_coeffs, size_t count, size_t nblocks, long long block_stride, size_t keep,
+                                                                                      void *d_work, size_t work_bytes, int restore_dc, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) size_t dspfft_topn_blocks_bytes(size_t count, size_t nblocks);
+extern "C" __attribute__((weak)) const char *dspfft_motion_last_error(void);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -1707,7 +1715,7 @@ int dither_store(const dspfft_plan_s *inv, const float *work, const Dither &dz, 
 }
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
                    const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice = true,
-                   const Dither *dither = nullptr);
+                   const Dither *dither = nullptr, size_t keep = 0, void *topn_work = nullptr, size_t topn_work_bytes = 0);
 
 // ---- the fused roundtrip: one call, checked (rt_check), then run by one of four strategies (roundtrip_core) ----
 // DSPFFT_NO_FUSED_ROUNDTRIP=1: no fused column kernel and no slices.  Read on every call (tests toggle it inside one process).
@@ -1723,12 +1731,28 @@ void motion_filter_of(const dspfft_motion_filter_params &fp, MotionFilter &mf)
 	motion_filter_set_divs(mf, fp.block_depth);
 }
 
+// The blocks of a plan pair as motion.c:652-668 sees them: `nblocks` runs of `count` floats (a block's whole embedding, :657), `stride` apart
+// in the working buffer.  False when the blocks are no such runs (interleaved batches, blocks lying side by side in a volume).
+struct TopnRuns { size_t count, nblocks; long long stride; };
+bool topn_runs_of(const dspfft_plan_s *fwd, const dspfft_plan_s *inv, TopnRuns &r)
+{
+	long long span = 1;
+	for (int a = 0; a < fwd->rank; a++) span += (long long)(std::max(fwd->n[a], inv->n[a]) - 1) * fwd->axes[a].os;
+	std::vector<Dim> dims;
+	for (const Dim &b : fwd->batches) if (b.n > 1) dims.push_back(Dim{b.n, b.os, b.os});
+	merge_dims(dims);
+	if (dims.size() > 1 || (dims.size() == 1 && dims[0].os < span)) return false;
+	r.count = (size_t)span; r.nblocks = dims.empty() ? 1 : (size_t)dims[0].n; r.stride = dims.empty() ? span : dims[0].os;
+	return true;
+}
+
 // One roundtrip call: its arguments, and what rt_check derives from them for the runners.
 // d_in8 / d_out8 non-NULL: 8-bit samples at the two ends (dspfft_execute_roundtrip_u8), d_out is then the float work buffer.
 struct RtCall {
 	dspfft_plan fwd, inv;
 	const float *d_in; float *d_out; const uint8_t *d_in8; uint8_t *d_out8; double mul8;
 	const dspfft_motion_filter_params *fp; unsigned long long *coded; void *stream;
+	size_t keep; void *topn_work; size_t topn_work_bytes;       // motion --coeff-limit (dspfft_execute_roundtrip_topn); keep = 0: none
 	// what rt_check adds (zero before)
 	const Pass *F, *I;                    // the forward plan's last pass and the inverse plan's first
 	bool rescale;                         // the inverse runs over other extents than the forward
@@ -1738,6 +1762,7 @@ struct RtCall {
 	int nf3[3], ni3[3];                   // region geometry of the two ends (rank padded to 3 with unit extents)
 	long long sw3[3], si3[3];
 	MotionFilter mf;
+	TopnRuns runs;                        // keep != 0 and not `block`: the blocks as contiguous runs of the working buffer
 };
 
 // every rejection of a roundtrip call; nothing has been launched when it returns
@@ -1787,11 +1812,26 @@ int rt_check(RtCall &c)
 	c.block = !c.rescale && block_roundtrip_ok(fwd, inv) && !((c.d_in8 ? 3u : 15u) & pin) && !((c.d_out8 ? 3u : 15u) & pout);
 	c.u8_first = pass_has_u8(fwd, fwd->passes[0]);
 	c.u8_last = pass_has_u8(inv, inv->passes[ni - 1]);
+	if (c.keep) {
+		// --coeff-limit: at or above the block's embedding count nothing is dropped (motion.c:654-657) and the call is the plain one
+		const bool runs = topn_runs_of(fwd, inv, c.runs);
+		if (c.block ? c.keep >= (size_t)fwd->blk.nx * fwd->blk.ny * fwd->blk.nz : (runs && c.keep >= c.runs.count)) c.keep = 0;
+	}
+	if (c.keep) {
+		if (!(c.block ? (bool)dspfft_block_topn_launch : (bool)dspfft_topn_blocks_launch && (bool)dspfft_topn_blocks_bytes))
+			return fail(-3, "roundtrip with a coefficient limit: not built into this library (the selection kernels are HIP-only, block_topn.hip and motion_ops.hip)");
+	}
 	if (c.block) return 0;
 	// the standalone filter finds a coefficient's position from its offset in a block-major embedding (minbuf_hw, block_depth); the
 	// blocks of a volume lying side by side are filtered by the fused block pass only, which knows each block's own coordinates
 	if (fp && fwd->has_block && !fwd->blk.rows_fast)
 		return fail(-2, "filtered roundtrip over the blocks of a volume needs the fused block pass: matching forward / inverse plans and 16-byte (8-bit: 4-byte) aligned buffers");
+	if (c.keep) {
+		if (c.runs.count == 0) return fail(-2, "roundtrip with a coefficient limit: every block must be one contiguous run of the working buffer (or go through the fused block pass)");
+		if (c.runs.count >= (1ull << 32)) return fail(-2, "roundtrip with a coefficient limit: a block of 2^32 coefficients or more");
+		const size_t need = dspfft_topn_blocks_bytes(c.runs.count, c.runs.nblocks);
+		if (c.topn_work_bytes < need || (need && !c.topn_work)) return fail(-1, "roundtrip with a coefficient limit: work buffer too small (dspfft_roundtrip_topn_work_bytes)");
+	}
 	if (c.rescale || !(c.d_in8 || c.d_out8)) return 0;
 	// the 8-bit buffers share the plans' element layout; the unfused conversions (rt_run_passes) walk whole spans
 	if (nf < 2 || ni < 2) return fail(-2, "8-bit roundtrip needs at least two transformed axes");
@@ -1815,7 +1855,23 @@ int rt_run_block(const RtCall &c)
 	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
 	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
 	a.filt = c.mf; a.coded = c.coded;
+	if (c.keep) {
+		BlockRtTopnArgs t;
+		static_cast<BlockRtArgs &>(t) = a;
+		t.keep = (unsigned int)c.keep;
+		if (int rc = dspfft_block_topn_launch(&t, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip with a coefficient limit): backend code %d", rc);
+		return 0;
+	}
 	if (int rc = be_launch_block_roundtrip(a, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip): backend code %d", rc);
+	return 0;
+}
+
+// motion.c:652-668 between the forward passes and the filter, over the blocks as runs; the DCs the filter's preserve_dc = dc restores
+// (:734) are those from before the selection (:650)
+int rt_topn(const RtCall &c)
+{
+	if (dspfft_topn_blocks_launch(c.d_out, c.runs.count, c.runs.nblocks, c.runs.stride, c.keep, c.topn_work, c.topn_work_bytes, motion_filter_restores_dc(c.mf), c.stream))
+		return fail(-4, "coefficient limit: %s", dspfft_motion_last_error ? dspfft_motion_last_error() : "launch failed");
 	return 0;
 }
 
@@ -1835,6 +1891,7 @@ int rt_run_rescale(const RtCall &c)
 		const Pass &P = fwd->passes[i];
 		if (int rc = run_pass<float>(fwd, P, (P.first && !c.d_in8) ? c.d_in : d_out, d_out, i + 1 == nf, c.stream)) return rc;
 	}
+	if (c.keep) if (int rc = rt_topn(c)) return rc;
 	if (c.fp && be_motion_filter(d_out, c.mf, (uint64_t)c.span, c.coded, c.stream)) return fail(-4, "filter launch failed");
 	for (size_t i = 0; i < ni; i++)
 		if (int rc = run_pass<float>(inv, inv->passes[i], (const float *)d_out, d_out, i + 1 == ni, c.stream)) return rc;
@@ -1866,7 +1923,8 @@ int rt_run_passes(const RtCall &c)
 	const bool listed = F.has_spec && I.has_spec && F.spec.id == I.spec.id;
 	const bool compiled = !listed && F.jit && I.jit && F.jit_fn_rt && F.jit_type == I.jit_type;      // kernels compiled at plan time (jit_kernels.h)
 	const bool fusable = F.type == Pass::COL && I.type == Pass::COL && (listed || compiled) && F.spec_nwg == I.spec_nwg &&
-	                     F.hostloop.empty() && I.hostloop.empty() && (15u & ((uintptr_t)src | (uintptr_t)d_out)) == 0 && !fused_roundtrip_off();
+	                     F.hostloop.empty() && I.hostloop.empty() && (15u & ((uintptr_t)src | (uintptr_t)d_out)) == 0 && !fused_roundtrip_off() &&
+	                     !c.keep;             // (the selection needs every coefficient of a block before the filter sees one)
 	PassArgs af, ai;
 	if (fusable) {
 		fill_args(af, F.spa, fwd, F, src, d_out, fwd->scale, Fuse());
@@ -1880,6 +1938,7 @@ int rt_run_passes(const RtCall &c)
 		} else if (int rc = be_launch_roundtrip(F.spec.id, af, ai, c.mf, c.coded, F.spec_nwg, stream)) return fail(-4, "kernel launch failed (fused roundtrip): backend code %d", rc);
 	} else {
 		if (int rc = run_pass<float>(fwd, F, src, d_out, true, stream)) return rc;
+		if (c.keep) if (int rc = rt_topn(c)) return rc;
 		if (c.fp && be_motion_filter(d_out, c.mf, (uint64_t)c.span, c.coded, stream)) return fail(-4, "filter launch failed");
 		if (int rc = run_pass<float>(inv, I, (const float *)d_out, d_out, ni == 1, stream)) return rc;
 	}
@@ -2024,15 +2083,16 @@ int roundtrip_sliced(const RtCall &c, const Dither *dither)
 
 // dither non-NULL (d_out8 NULL): the inverse transform ends in d_out as floats and the dither kernel stores dither->out8 from there.
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
-                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice, const Dither *dither)
+                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice, const Dither *dither,
+                   size_t keep, void *topn_work, size_t topn_work_bytes)
 {
-	RtCall c = {fwd, inv, d_in, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream};
+	RtCall c = {fwd, inv, d_in, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream, keep, topn_work, topn_work_bytes};
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
 	if (c.block) rc = rt_run_block(c);
 	else if (c.rescale) rc = rt_run_rescale(c);
 	else {
-		if (may_slice && d_in8 && (d_out8 || dither) && c.u8_first && c.u8_last && c.F->axis == c.I->axis && (15u & (uintptr_t)d_out) == 0 && !fused_roundtrip_off())
+		if (may_slice && !c.keep && d_in8 && (d_out8 || dither) && c.u8_first && c.u8_last && c.F->axis == c.I->axis && (15u & (uintptr_t)d_out) == 0 && !fused_roundtrip_off())
 			rc = roundtrip_sliced(c, dither);
 		if (rc) return rc < 0 ? rc : 0;          // in slices: every slice has stored or dithered its own frames
 		rc = rt_run_passes(c);
@@ -2054,6 +2114,28 @@ extern "C" int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, con
 {
 	if (!d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
 	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream);
+}
+
+extern "C" size_t dspfft_roundtrip_topn_work_bytes(dspfft_plan fwd, dspfft_plan inv)
+{
+	TopnRuns r;
+	if (!fwd || !inv || fwd->f64 || inv->f64 || fwd->rank != inv->rank || block_roundtrip_ok(fwd, inv) || !dspfft_topn_blocks_bytes || !topn_runs_of(fwd, inv, r)) return 0;
+	return dspfft_topn_blocks_bytes(r.count, r.nblocks);
+}
+
+extern "C" int dspfft_execute_roundtrip_topn(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const dspfft_motion_filter_params *fp, size_t keep,
+                                             void *d_topn_work, size_t work_bytes, unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (!d_in) return fail(-1, "null plan or buffer");
+	return roundtrip_core(fwd, inv, d_in, d_out, nullptr, nullptr, 1.0, fp, d_coeffs_coded, stream, true, nullptr, keep, d_topn_work, work_bytes);
+}
+
+extern "C" int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
+                                                const dspfft_motion_filter_params *fp, size_t keep, void *d_topn_work, size_t work_bytes,
+                                                unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (!d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
+	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream, true, nullptr, keep, d_topn_work, work_bytes);
 }
 
 extern "C" int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,

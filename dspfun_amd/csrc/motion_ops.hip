@@ -10,10 +10,12 @@
 #include <rocprim/rocprim.hpp>
 #include <math.h>
 #include <stdio.h>
+#include <algorithm>
 
 #include "../../include/dspfft.h"
 #include "motion_filter.h"
 #include "trc_core.h"
+#include "topn_core.h"
 
 static_assert(dspfft::MOTION_MODE_NONE == DSPFFT_MOTION_NONE && dspfft::MOTION_MODE_ABS == DSPFFT_MOTION_ABS && dspfft::MOTION_MODE_SHIFT == DSPFFT_MOTION_SHIFT &&
               dspfft::MOTION_MODE_FLAT == DSPFFT_MOTION_FLAT && dspfft::MOTION_MODE_COPY == DSPFFT_MOTION_COPY, "motion_filter.h's modes are dspfft.h's");
@@ -76,12 +78,22 @@ __global__ void motion_linear_kernel(float *dst, const float *src, Reg r, int st
 }
 
 // ---- top-N by magnitude: radix select on the bits of |c| (monotone for non-negative floats) ----
+// Runs too long for a workgroup's LDS (a 1920 x 1080 frame).  blockIdx.y is the run: one SelState and one histogram per run; the flag and
+// rank arrays hold the runs of a launch back to back.
 struct SelState { uint32_t prefix, mask, remaining, pad; };       // keys matching (key & mask) == prefix are still candidates
-__global__ void topn_hist_kernel(uint32_t *hist, const float *c, size_t n, const SelState *st, int shift)
+__global__ void topn_init_kernel(SelState *st, uint32_t *hist, uint32_t runs, uint32_t keep)
+{
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)runs * 256; i += (size_t)gridDim.x * blockDim.x) {
+		hist[i] = 0;
+		if (i < runs) st[i] = SelState{0u, 0u, keep, 0u};
+	}
+}
+__global__ void topn_hist_kernel(uint32_t *hist, const float *c, size_t n, long long stride, const SelState *st, int shift)
 {
 	__shared__ uint32_t h[256];
 	h[threadIdx.x] = 0;
 	__syncthreads();
+	c += (long long)blockIdx.y * stride; hist += (size_t)blockIdx.y * 256; st += blockIdx.y;
 	const uint32_t prefix = st->prefix, mask = st->mask;
 	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
 		const uint32_t k = __float_as_uint(fabsf(c[i]));
@@ -90,10 +102,11 @@ __global__ void topn_hist_kernel(uint32_t *hist, const float *c, size_t n, const
 	__syncthreads();
 	if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
 }
-// one thread: walk the 256 bins from the top, find the bin holding the `remaining`-th largest candidate
+// one thread per run: walk the 256 bins from the top, find the bin holding the `remaining`-th largest candidate
 __global__ void topn_pick_kernel(uint32_t *hist, SelState *st, int shift)
 {
-	if (threadIdx.x || blockIdx.x) return;
+	if (threadIdx.x) return;
+	hist += (size_t)blockIdx.y * 256; st += blockIdx.y;
 	uint32_t rem = st->remaining;
 	int b = 255;
 	for (; b > 0; b--) { if (hist[b] >= rem) break; rem -= hist[b]; }
@@ -102,18 +115,55 @@ __global__ void topn_pick_kernel(uint32_t *hist, SelState *st, int shift)
 	st->remaining = rem;                      // how many of the candidates in bin b (and, after the last pass, equal to the threshold) to keep
 	for (int i = 0; i < 256; i++) hist[i] = 0;
 }
-__global__ void topn_flag_kernel(uint32_t *tie, const float *c, size_t n, const SelState *st)
+__global__ void topn_flag_kernel(uint32_t *tie, const float *c, size_t n, long long stride, const SelState *st)
 {
-	const uint32_t T = st->prefix;
+	c += (long long)blockIdx.y * stride; tie += (size_t)blockIdx.y * n;
+	const uint32_t T = st[blockIdx.y].prefix;
 	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
 		tie[i] = __float_as_uint(fabsf(c[i])) == T ? 1u : 0u;
 }
-__global__ void topn_apply_kernel(float *c, const uint32_t *rank, size_t n, const SelState *st)
+// rank: the exclusive scan of ALL the launch's flags; a tie's rank within its run is that minus the value at the run's start
+__global__ void topn_apply_kernel(float *c, const uint32_t *rank, size_t n, long long stride, const SelState *st)
 {
-	const uint32_t T = st->prefix, keep_ties = st->remaining;
+	c += (long long)blockIdx.y * stride; rank += (size_t)blockIdx.y * n;
+	const uint32_t T = st[blockIdx.y].prefix, keep_ties = st[blockIdx.y].remaining, rank0 = rank[0];
 	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
 		const uint32_t k = __float_as_uint(fabsf(c[i]));
-		if (!(k > T || (k == T && rank[i] < keep_ties))) c[i] = 0.f;
+		if (!(k > T || (k == T && rank[i] - rank0 < keep_ties))) c[i] = 0.f;
+	}
+}
+// element 0 of every run aside (restore = 0) and back (restore = 1): the roundtrip's preserve_dc = dc (motion.c:650,734)
+__global__ void topn_dc_kernel(float *c, long long stride, float *save, size_t nblocks, int restore)
+{
+	for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < nblocks; r += (size_t)gridDim.x * blockDim.x) {
+		if (restore) c[(long long)r * stride] = save[r]; else save[r] = c[(long long)r * stride];
+	}
+}
+
+// Runs of up to TOPN_LDS_MAX floats: topn_core.h's selection, the code the fused block kernel runs (block_topn.hip).  A wave owns a run
+// (runs below 64 floats: 64 / L of them share a wave) in an LDS area of its own; every lane loads, selects over and stores the elements
+// e = sl, sl + L, ... of its run, so no lane reads what another wrote and the kernel needs no barrier.
+// LDS is here a per-lane staging area only, and at 4096 floats a run it is 64 KB a workgroup (two workgroups per CU): the price of running
+// the one selection routine the fused kernel runs, which takes its keys from and zeroes its losers in LDS.
+enum { TOPN_LDS_MAX = 4096, TOPN_THREADS = 256 };
+template <int K>
+__global__ void __launch_bounds__(TOPN_THREADS) topn_blocks_lds_kernel(float *c, int count, size_t nblocks, long long stride, uint32_t keep, int L, int restore_dc)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char topn_lds_raw[];
+	const int lane = threadIdx.x & 63, sl = lane & (L - 1), per_wave = 64 / L, slot = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * per_wave + lane / L;
+	const size_t per_wg = (size_t)(TOPN_THREADS / 64) * per_wave;
+	float *mine = reinterpret_cast<float *>(topn_lds_raw) + (size_t)slot * count;
+	for (size_t r0 = blockIdx.x * per_wg; r0 < nblocks; r0 += gridDim.x * per_wg) {       // (uniform over the workgroup)
+		const size_t r = r0 + slot;
+		const bool active = r < nblocks;
+		float *g = c + (long long)(active ? r : r0) * stride;
+		if (active) for (int e = sl; e < count; e += L) mine[e] = g[e];
+		const bool lead = restore_dc && active && sl == 0;
+		float dc = 0.f;
+		if (lead) dc = mine[0];
+		dspfft::topn_select_lds<K, 0>(mine, 0, count, keep, L, active);
+		if (lead) mine[0] = dc;
+		if (active) for (int e = sl; e < count; e += L) g[e] = mine[e];
 	}
 }
 
@@ -177,6 +227,81 @@ extern "C" __attribute__((visibility("hidden"))) int dspfft_motion_linear_launch
 	return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+namespace {
+// ---- the global path's work area: [R SelStates | R histograms] rounded to 4 KB, R * count flags, R * count ranks, the scan's storage ----
+// R runs go through one set of launches: as many as 2^26 elements' worth (512 MB of flags and ranks), at most 65535 (gridDim.y)
+size_t topn_runs_per_launch(size_t count, size_t nblocks) { return std::max<size_t>(1, std::min(std::min<size_t>(nblocks, 65535), ((size_t)1 << 26) / count)); }
+size_t topn_head_bytes(size_t R) { return (((R * sizeof(SelState) + 255) & ~(size_t)255) + R * 1024 + 4095) & ~(size_t)4095; }
+size_t topn_slab_bytes(size_t count, size_t R) { return (R * count * 4 + 255) & ~(size_t)255; }
+size_t topn_global_bytes(size_t count, size_t R) { return topn_head_bytes(R) + 2 * topn_slab_bytes(count, R) + scan_temp(R * count); }
+
+int topn_global(float *c, size_t count, size_t nblocks, long long stride, size_t keep, char *base, hipStream_t s)
+{
+	const size_t R = topn_runs_per_launch(count, nblocks);
+	const size_t slab = topn_slab_bytes(count, R);
+	SelState *st = (SelState *)base;
+	uint32_t *hist = (uint32_t *)(base + ((R * sizeof(SelState) + 255) & ~(size_t)255));
+	uint32_t *tie = (uint32_t *)(base + topn_head_bytes(R)), *rank = (uint32_t *)(base + topn_head_bytes(R) + slab);
+	void *temp = base + topn_head_bytes(R) + 2 * slab;
+	size_t tb = scan_temp(R * count);
+	for (size_t r0 = 0; r0 < nblocks; r0 += R) {
+		const uint32_t runs = (uint32_t)std::min(R, nblocks - r0);
+		float *c0 = c + (long long)r0 * stride;
+		const dim3 grid(mgrid(count), runs);
+		hipLaunchKernelGGL(topn_init_kernel, dim3(mgrid((size_t)runs * 256)), dim3(256), 0, s, st, hist, runs, (uint32_t)keep);
+		for (int shift = 24; shift >= 0; shift -= 8) {
+			hipLaunchKernelGGL(topn_hist_kernel, grid, dim3(256), 0, s, hist, c0, count, stride, st, shift);
+			hipLaunchKernelGGL(topn_pick_kernel, dim3(1, runs), dim3(64), 0, s, hist, st, shift);
+		}
+		// elements equal to the threshold: the first `remaining` of them in buffer order are kept (the reference leaves ties to qsort)
+		hipLaunchKernelGGL(topn_flag_kernel, grid, dim3(256), 0, s, tie, c0, count, stride, st);
+		if (rocprim::exclusive_scan(temp, tb, tie, rank, 0u, (size_t)runs * count, rocprim::plus<uint32_t>(), s) != hipSuccess) return -4;
+		hipLaunchKernelGGL(topn_apply_kernel, grid, dim3(256), 0, s, c0, rank, count, stride, st);
+	}
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+template <int K>
+int topn_lds_launch(float *c, size_t count, size_t nblocks, long long stride, size_t keep, int L, int restore_dc, hipStream_t s)
+{
+	const size_t per_wg = (size_t)(TOPN_THREADS / 64) * (64 / L), lds = per_wg * count * sizeof(float);
+	static int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void *>(topn_blocks_lds_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+	if (attr) return -4;
+	const size_t nwg = std::min<size_t>((nblocks + per_wg - 1) / per_wg, 1u << 20);
+	hipLaunchKernelGGL(topn_blocks_lds_kernel<K>, dim3((unsigned)nwg), dim3(TOPN_THREADS), lds, s, c, (int)count, nblocks, stride, (uint32_t)keep, L, restore_dc);
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+size_t topn_blocks_bytes(size_t count, size_t nblocks)
+{
+	if (count <= TOPN_LDS_MAX) return 0;
+	return topn_global_bytes(count, topn_runs_per_launch(count, nblocks)) + ((nblocks * 4 + 255) & ~(size_t)255);
+}
+
+// the arguments have been checked; 0 < keep < count
+int topn_blocks_run(float *c, size_t count, size_t nblocks, long long stride, size_t keep, void *d_work, int restore_dc, hipStream_t s)
+{
+	if (count <= TOPN_LDS_MAX) {
+		int L = 64;
+		while (L / 2 >= (int)count) L /= 2;
+		const size_t k = (count + 63) / 64;
+		if (k <= 1) return topn_lds_launch<1>(c, count, nblocks, stride, keep, L, restore_dc, s);
+		if (k <= 4) return topn_lds_launch<4>(c, count, nblocks, stride, keep, L, restore_dc, s);
+		if (k <= 8) return topn_lds_launch<8>(c, count, nblocks, stride, keep, L, restore_dc, s);
+		if (k <= 16) return topn_lds_launch<16>(c, count, nblocks, stride, keep, L, restore_dc, s);
+		if (k <= 32) return topn_lds_launch<32>(c, count, nblocks, stride, keep, L, restore_dc, s);
+		return topn_lds_launch<64>(c, count, nblocks, stride, keep, L, restore_dc, s);
+	}
+	const size_t R = topn_runs_per_launch(count, nblocks);
+	float *dcs = (float *)((char *)d_work + topn_global_bytes(count, R));
+	if (restore_dc) hipLaunchKernelGGL(topn_dc_kernel, dim3(mgrid(nblocks)), dim3(256), 0, s, c, stride, dcs, nblocks, 0);
+	if (int rc = topn_global(c, count, nblocks, stride, keep, (char *)d_work, s)) return rc;
+	if (restore_dc) hipLaunchKernelGGL(topn_dc_kernel, dim3(mgrid(nblocks)), dim3(256), 0, s, c, stride, dcs, nblocks, 1);
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+}  // namespace
+
 extern "C" size_t dspfft_motion_topn_work_bytes(size_t count) { return 2 * ((count * 4 + 255) & ~(size_t)255) + 4096 + scan_temp(count); }
 
 extern "C" int dspfft_motion_topn(float *d_coeffs, size_t count, size_t keep, void *d_work, size_t work_bytes, void *stream)
@@ -187,21 +312,39 @@ extern "C" int dspfft_motion_topn(float *d_coeffs, size_t count, size_t keep, vo
 	hipStream_t s = (hipStream_t)stream;
 	if (keep >= count) return 0;
 	if (!keep) return hipMemsetAsync(d_coeffs, 0, count * 4, s) == hipSuccess ? 0 : -4;
-	const size_t slab = (count * 4 + 255) & ~(size_t)255;
-	char *base = (char *)d_work;
-	SelState *st = (SelState *)base;
-	uint32_t *hist = (uint32_t *)(base + 1024), *tie = (uint32_t *)(base + 4096), *rank = (uint32_t *)(base + 4096 + slab);
-	void *temp = base + 4096 + 2 * slab;
-	size_t tb = scan_temp(count);
-	SelState init = {0u, 0u, (uint32_t)keep, 0u};
-	if (hipMemcpyAsync(st, &init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(hist, 0, 1024, s) != hipSuccess) return -4;
-	for (int shift = 24; shift >= 0; shift -= 8) {
-		hipLaunchKernelGGL(topn_hist_kernel, dim3(mgrid(count)), dim3(256), 0, s, hist, d_coeffs, count, st, shift);
-		hipLaunchKernelGGL(topn_pick_kernel, dim3(1), dim3(64), 0, s, hist, st, shift);
-	}
-	// elements equal to the threshold: the first `remaining` of them in buffer order are kept (the reference leaves ties to qsort)
-	hipLaunchKernelGGL(topn_flag_kernel, dim3(mgrid(count)), dim3(256), 0, s, tie, d_coeffs, count, st);
-	if (rocprim::exclusive_scan(temp, tb, tie, rank, 0u, count, rocprim::plus<uint32_t>(), s) != hipSuccess) return -4;
-	hipLaunchKernelGGL(topn_apply_kernel, dim3(mgrid(count)), dim3(256), 0, s, d_coeffs, rank, count, st);
-	return hipGetLastError() == hipSuccess ? 0 : -4;
+	return topn_global(d_coeffs, count, 1, (long long)count, keep, (char *)d_work, s);     // one run: the work area is the one this call has always had
 }
+
+extern "C" size_t dspfft_motion_topn_blocks_work_bytes(size_t count, size_t nblocks)
+{
+	if (!count || !nblocks || count >= (1ull << 32)) return 0;
+	return topn_blocks_bytes(count, nblocks);
+}
+
+static int topn_blocks_checked(float *d_coeffs, size_t count, size_t nblocks, long long block_stride, size_t keep, void *d_work, size_t work_bytes, int restore_dc, void *stream)
+{
+	if (!d_coeffs || !count || !nblocks) return mbad("bad arguments");
+	if (count >= (1ull << 32)) return mbad("top-N select addresses a run with 32-bit counts");
+	if (nblocks > 1 && (block_stride < 0 || (unsigned long long)block_stride < count)) return mbad("top-N select: the runs overlap (block_stride < count)");
+	hipStream_t s = (hipStream_t)stream;
+	if (keep >= count) return 0;
+	if (!keep) return hipMemset2DAsync(d_coeffs, (nblocks > 1 ? (size_t)block_stride : count) * 4, 0, count * 4, nblocks, s) == hipSuccess ? 0 : -4;
+	const size_t need = topn_blocks_bytes(count, nblocks);
+	if (need && !d_work) return mbad("bad arguments: runs of this length need a work buffer (dspfft_motion_topn_blocks_work_bytes)");
+	if (work_bytes < need) return mbad("work buffer too small: dspfft_motion_topn_blocks_work_bytes");
+	return topn_blocks_run(d_coeffs, count, nblocks, nblocks > 1 ? block_stride : (long long)count, keep, d_work, restore_dc, s);
+}
+
+extern "C" int dspfft_motion_topn_blocks(float *d_coeffs, size_t count, size_t nblocks, long long block_stride, size_t keep, void *d_work, size_t work_bytes, void *stream)
+{
+	return topn_blocks_checked(d_coeffs, count, nblocks, block_stride, keep, d_work, work_bytes, 0, stream);
+}
+
+/* the roundtrip's selection stage (engine.cpp reaches the two through weak references): restore_dc puts every run's element 0 back as it was
+ * before the selection.  The error text is dspfft_motion_last_error's. */
+extern "C" __attribute__((visibility("hidden"))) int dspfft_topn_blocks_launch(float *d_coeffs, size_t count, size_t nblocks, long long block_stride, size_t keep,
+                                                                                void *d_work, size_t work_bytes, int restore_dc, void *stream)
+{
+	return topn_blocks_checked(d_coeffs, count, nblocks, block_stride, keep, d_work, work_bytes, restore_dc, stream);
+}
+extern "C" __attribute__((visibility("hidden"))) size_t dspfft_topn_blocks_bytes(size_t count, size_t nblocks) { return dspfft_motion_topn_blocks_work_bytes(count, nblocks); }

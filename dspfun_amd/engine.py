@@ -175,21 +175,45 @@ class Plan:
         fp.preserve_dc = filter.get("preserve_dc", 0); fp.grey_add = filter.get("grey_add", 0.0); fp.quantizer = filter.get("quantizer", 0.0)
         return fp
 
-    def roundtrip(self, inv, d_in, d_out=None, filter=None, d_coded=0, stream=0):
+    def _topn_work(self, inv, topn_work):
+        """(pointer, bytes) of the selection's scratch: the caller's uint8 device tensor, or one allocated here when the plans need any"""
+        if topn_work is None:
+            need = int(self._lib.dspfft_roundtrip_topn_work_bytes(self._h, inv._h))
+            if not need:
+                return None, 0, None
+            import torch
+            topn_work = torch.empty(need, dtype=torch.uint8, device="cuda")
+        return C.c_void_p(topn_work.data_ptr()), topn_work.numel() * topn_work.element_size(), topn_work
+
+    def roundtrip(self, inv, d_in, d_out=None, filter=None, d_coded=0, stream=0, coeff_limit=0, topn_work=None):
         """motion/motion.c:641-753: self (REDFT10) -> filter -> inv (REDFT01, created with first_axis_first=True), the middle axis
         fused into one launch when both plans have a specialised column kernel.  filter: dict with the fields of
-        dspfft_motion_filter_params, or None."""
+        dspfft_motion_filter_params, or None.  coeff_limit: motion --coeff-limit, the coefficients kept per block ahead of the filter
+        (dspfft_execute_roundtrip_topn; 0: none); topn_work: a uint8 device tensor of dspfft_roundtrip_topn_work_bytes, allocated per
+        call when None and the plans need one."""
         d_out = d_in if d_out is None else d_out
         fp = self._filter_params(filter)
-        self._check(self._lib.dspfft_execute_roundtrip(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), C.byref(fp) if fp is not None else None,
-                                                       C.c_void_p(d_coded or None), C.c_void_p(stream)))
+        fpp = C.byref(fp) if fp is not None else None
+        if not coeff_limit:
+            self._check(self._lib.dspfft_execute_roundtrip(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), fpp, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+            return
+        wp, wb, _hold = self._topn_work(inv, topn_work)
+        self._check(self._lib.dspfft_execute_roundtrip_topn(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), fpp, int(coeff_limit), wp, wb,
+                                                            C.c_void_p(d_coded or None), C.c_void_p(stream)))
 
-    def roundtrip_u8(self, inv, d_in_u8, d_out_u8, d_work, out_mul, filter=None, d_coded=0, stream=0):
+    def roundtrip_u8(self, inv, d_in_u8, d_out_u8, d_work, out_mul, filter=None, d_coded=0, stream=0, coeff_limit=0, topn_work=None):
         """the same with motion's 8-bit samples at both ends (motion.c:617-640, :760-776): u8 in, float work buffer, u8 out =
-        quantise(value * out_mul); the conversions ride on the first and last row passes when those are planar specialised passes"""
+        quantise(value * out_mul); the conversions ride on the first and last row passes when those are planar specialised passes.
+        coeff_limit, topn_work: as roundtrip's (dspfft_execute_roundtrip_u8_topn)."""
         fp = self._filter_params(filter)
-        self._check(self._lib.dspfft_execute_roundtrip_u8(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
-                                                          C.byref(fp) if fp is not None else None, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+        fpp = C.byref(fp) if fp is not None else None
+        if not coeff_limit:
+            self._check(self._lib.dspfft_execute_roundtrip_u8(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
+                                                              fpp, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+            return
+        wp, wb, _hold = self._topn_work(inv, topn_work)
+        self._check(self._lib.dspfft_execute_roundtrip_u8_topn(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
+                                                               fpp, int(coeff_limit), wp, wb, C.c_void_p(d_coded or None), C.c_void_p(stream)))
 
     def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0):
         """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
@@ -238,6 +262,25 @@ def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nbloc
     g.block_step[:] = [int(v) for v in block_step]
     if lib.dspfft_motion_dither_u8(C.c_void_p(d_pix), C.c_void_p(d_coeffs), C.byref(g), float(scalefactor), float(normalization), C.c_void_p(stream)):
         raise DspfftError(lib.dspfft_motion_last_error().decode())
+
+
+def motion_topn_blocks(t, count, keep, stride=None, stream=None, lib=None):
+    """dspfft_motion_topn_blocks in place on a contiguous float32 device tensor: motion --coeff-limit in each of its runs of `count` floats,
+    `stride` floats apart (default: count, the runs back to back); what lies between the runs stays.  Returns t."""
+    lib = lib or _lib.load()
+    import torch
+    count, keep = int(count), int(keep)
+    stride = count if stride is None else int(stride)
+    assert t.is_contiguous() and t.element_size() == 4 and count >= 1 and stride >= count
+    nblocks = (t.numel() - count) // stride + 1
+    assert nblocks >= 1
+    need = int(lib.dspfft_motion_topn_blocks_work_bytes(count, nblocks))
+    work = torch.empty(need, dtype=torch.uint8, device=t.device) if need else None
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    if lib.dspfft_motion_topn_blocks(C.c_void_p(t.data_ptr()), count, nblocks, stride, keep, _ptr(work), need, C.c_void_p(stream)):
+        raise DspfftError(lib.dspfft_motion_last_error().decode())
+    return t
 
 
 def trc_id(trc, lib=None):

@@ -269,6 +269,30 @@ int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const u
                                        double scalefactor, double normalization, const dspfft_motion_filter_params *filter,
                                        unsigned long long *d_coeffs_coded, void *hip_stream);
 
+/* The two calls above with motion's --coeff-limit (motion/motion.c:652-668) between the forward transform and the filter: of every block's
+ * coefficients -- as the forward plan writes them, which with motion's per-axis index-0 factors (dspfft_plan_set_axis_scale0, :644-647) are
+ * the uniform-range coefficients the reference selects among -- the `keep` of largest magnitude stay and the rest become zero, before the
+ * filter acts (:652 is ahead of :683).  The rule is dspfft_motion_topn_blocks' (below): the key is the bit pattern of |c|, ties at the
+ * threshold go to the earliest in the block's own buffer order (z, then y, then x), NaNs are outside the contract.  The reference selects
+ * over `mincomponent`, the largest component's buffer; for a smaller component the remainder is zeros, so per block this is a selection
+ * over the block's own embedding.  preserve_dc = dc restores the block's DC as it was BEFORE the selection (:650, :734).
+ * keep == 0 (the reference's `if(coeff_limit)`) or keep >= the block's embedding count: the call IS the plain one -- same kernels, same
+ * bytes, every path of it, and d_topn_work may be NULL.  Otherwise:
+ *   small blocks on the fused block pass (a volume's blocks, block-major stacks): ONE kernel as before, with the selection in the LDS tile
+ *     between the forward and the inverse axes; needs no work buffer (dspfft_roundtrip_topn_work_bytes is 0 for such a plan pair)
+ *   block-major stacks with DSPFFT_NO_BLOCK=1, clips of per-frame blocks, one 3-D block, scaled != block (count = the whole embedding,
+ *     :657): the forward passes, dspfft_motion_topn_blocks over the blocks as contiguous runs of the working buffer, the stand-alone
+ *     filter, the inverse passes.  For this call there is then NO fused column roundtrip and the clip does NOT run in slices: the
+ *     selection needs every coefficient of a block before the filter sees one.  d_topn_work holds dspfft_roundtrip_topn_work_bytes.
+ * Blocks that are no contiguous runs (interleaved batches; a volume's blocks on misaligned buffers) are refused (-2), and a library built
+ * without the HIP selection kernels returns -3 for a keep in range, in both cases with nothing launched.  There is no dithered variant. */
+size_t dspfft_roundtrip_topn_work_bytes(dspfft_plan fwd, dspfft_plan inv);
+int dspfft_execute_roundtrip_topn(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const dspfft_motion_filter_params *filter,
+                                  size_t keep, void *d_topn_work, size_t work_bytes, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
+                                     const dspfft_motion_filter_params *filter, size_t keep, void *d_topn_work, size_t work_bytes,
+                                     unsigned long long *d_coeffs_coded, void *hip_stream);
+
 /* Replaces fftw(destroy_plan). */
 void dspfft_destroy_plan(dspfft_plan plan);
 
@@ -480,6 +504,15 @@ int dspfft_motion_dither_u8(uint8_t *d_pix, const float *d_coeffs, const dspfft_
  * depends on qsort; here the earliest in buffer order are kept -- documented, deterministic. */
 size_t dspfft_motion_topn_work_bytes(size_t count);
 int dspfft_motion_topn(float *d_coeffs, size_t count, size_t keep, void *d_work, size_t work_bytes, void *hip_stream);
+/* The same selection in each of `nblocks` contiguous runs of `count` floats, `block_stride` floats apart (>= count): a block-major stack of
+ * blocks, the frames of a clip, one 3-D block (motion --coeff-limit with -b 8x8x8, -b 0x0x1, one block).  keep == 0 zeroes every run, keep >=
+ * count is a no-op; what lies between the runs is never touched.  Runs of up to 4096 floats are selected in LDS, a wave per run, by the code
+ * the fused block roundtrip runs (topn_core.h: 31 ballot rounds over the bits of |c|), and need no work buffer (d_work may be NULL, the byte
+ * count is 0); longer ones take the radix select above with one histogram per run, as many runs per launch as 2^26 elements' worth.
+ * The reference selects over `mincomponent`, the largest component's buffer: a run is the block's own embedding. */
+size_t dspfft_motion_topn_blocks_work_bytes(size_t count, size_t nblocks);
+int dspfft_motion_topn_blocks(float *d_coeffs, size_t count, size_t nblocks, long long block_stride, size_t keep, void *d_work, size_t work_bytes,
+                              void *hip_stream);
 const char *dspfft_motion_last_error(void);
 
 /* scan/scan.c:451-459 arithmetic: sum += image (len floats). */
