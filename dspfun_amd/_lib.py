@@ -32,6 +32,7 @@ SYMBOLS = [
     "dspfft_scanframes_compose", "dspfft_scanframes_parity", "dspfft_scanframes_destroy",
     "dspfft_trc_from_name", "dspfft_trc_name", "dspfft_trc_apply_f32", "dspfft_scanframes_set_trc", "dspfft_zoomanim_set_trc",
     "dspfft_motion_load_f32_linear", "dspfft_motion_store_f32_linear",
+    "dspfft_plan_set_u8_trc", "dspfft_u8_to_f32_trc", "dspfft_f32_to_u8_trc", "dspfft_motion_load_u8_linear", "dspfft_motion_store_u8_linear", "dspfft_motion_dither_u8_trc",
     "dspfft_applybasis_work_floats", "dspfft_applybasis_partsums",
     "dspfft_applybasis_work_floats_ex", "dspfft_applybasis_partsums_ex", "dspfft_applybasis_render",
     "dspfft_motion_load_u8", "dspfft_motion_store_u8", "dspfft_motion_load_f32", "dspfft_motion_store_f32", "dspfft_motion_topn_work_bytes", "dspfft_motion_topn", "dspfft_motion_last_error", "dspfft_motion_dither_u8",
@@ -179,6 +180,12 @@ def bind(lib):
         lib.dspfft_zoomanim_set_trc.argtypes = [vp, C.c_int]
         lib.dspfft_motion_load_f32_linear.argtypes = [vp, vp, ip, ip, C.c_int, vp]
         lib.dspfft_motion_store_f32_linear.argtypes = [vp, vp, ip, ip, C.c_double, C.c_double, C.c_int, vp]
+    if hasattr(lib, "dspfft_plan_set_u8_trc"):   # (likewise)
+        lib.dspfft_plan_set_u8_trc.argtypes = [vp, C.c_int]
+        lib.dspfft_u8_to_f32_trc.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
+        lib.dspfft_f32_to_u8_trc.argtypes = [vp, vp, C.c_double, C.c_uint64, C.c_int, vp]
+        lib.dspfft_motion_load_u8_linear.argtypes = [vp, vp, ip, ip, C.c_int, vp]
+        lib.dspfft_motion_store_u8_linear.argtypes = [vp, vp, ip, ip, C.c_double, C.c_double, C.c_int, vp]
     if hasattr(lib, "dspfft_zoom_product"):      # HIP-only entry points (absent from the CPU emulation used in tests)
         lib.dspfft_zoom_ncomponents.restype = C.c_size_t
         lib.dspfft_zoom_ncomponents.argtypes = [C.c_double, C.c_double, C.c_size_t]
@@ -218,6 +225,8 @@ def bind(lib):
             lib.dspfft_motion_topn_blocks.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_longlong, C.c_size_t, vp, C.c_size_t, vp]
         lib.dspfft_motion_last_error.restype = C.c_char_p
         lib.dspfft_motion_dither_u8.argtypes = [vp, vp, C.POINTER(DitherGeom), C.c_double, C.c_double, vp]
+        if hasattr(lib, "dspfft_motion_dither_u8_trc"):
+            lib.dspfft_motion_dither_u8_trc.argtypes = [vp, vp, C.POINTER(DitherGeom), C.c_double, C.c_double, C.c_int, vp]
         lib.dspfft_scan_pruned_accumulate.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         lib.dspfft_scan_pruned_work_floats.restype = C.c_size_t
         lib.dspfft_scan_pruned_work_floats.argtypes = [C.c_int, C.c_int, C.c_int]

@@ -16,6 +16,7 @@
 #include "dct_core.h"
 #include "elementwise_core.h"
 #include "motion_filter.h"
+#include "trc_u8_core.h"
 
 namespace dspfft {
 
@@ -83,9 +84,13 @@ DSP_HD void block_line_of(const BlockGeom &a, int l, int rows, int cnt, int &row
 	if (a.rows_fast) { g = l / rows; row = l - g * rows; } else { row = l / cnt; g = l - row * cnt; }
 }
 
-// phase x, forward side: load (float or 8-bit) + x transform into the tile
-template <int NX, int NY, int NZ, int KIND, bool U8>
-DSP_HD void block_load_x(const BlockGeom &a, const TinyArgs &tx, const float *in, const uint8_t *in8, float *lds, long long bin, int cnt, int tid)
+// motion --linear on 8-bit samples (trc_u8_core.h) at the two ends of the fused roundtrip: the tables as the kernel holds them (in LDS behind
+// the tile); lut / thr NULL: that end converts plainly
+struct BlockTrc { const float *lut; const double *thr; TrcParams tp; };
+
+// phase x, forward side: load (float or 8-bit; TRC: 8-bit through the decode table) + x transform into the tile
+template <int NX, int NY, int NZ, int KIND, bool U8, bool TRC = false>
+DSP_HD void block_load_x(const BlockGeom &a, const TinyArgs &tx, const float *in, const uint8_t *in8, float *lds, long long bin, int cnt, int tid, const BlockTrc *t = nullptr)
 {
 	const int lines = NZ * NY * cnt;
 	for (int l = tid; l < lines; l += BLOCK_THREADS) {
@@ -100,7 +105,10 @@ DSP_HD void block_load_x(const BlockGeom &a, const TinyArgs &tx, const float *in
 				uint32_t w4;
 				__builtin_memcpy(&w4, in8 + off + 4 * j, 4);
 #pragma unroll
-				for (int q = 0; q < 4; q++) x[4 * j + q] = (float)((w4 >> (8 * q)) & 0xffu);
+				for (int q = 0; q < 4; q++) {
+					if constexpr (TRC) x[4 * j + q] = t->lut ? t->lut[(w4 >> (8 * q)) & 0xffu] : (float)((w4 >> (8 * q)) & 0xffu);
+					else x[4 * j + q] = (float)((w4 >> (8 * q)) & 0xffu);
+				}
 			}
 		} else {
 #pragma unroll
@@ -115,9 +123,9 @@ DSP_HD void block_load_x(const BlockGeom &a, const TinyArgs &tx, const float *in
 		for (int j = 0; j < NX / 4; j++) { float4 v; v.x = o[4 * j]; v.y = o[4 * j + 1]; v.z = o[4 * j + 2]; v.w = o[4 * j + 3]; q[j] = v; }
 	}
 }
-// phase x, inverse side: x transform out of the tile + store (float or quantised 8-bit, motion.c:760-776)
-template <int NX, int NY, int NZ, int KIND, bool U8>
-DSP_HD void block_store_x(const BlockGeom &a, const TinyArgs &tx, float *out, uint8_t *out8, double mul8, const float *lds, long long bout, int cnt, int tid)
+// phase x, inverse side: x transform out of the tile + store (float or quantised 8-bit, motion.c:760-776; TRC: the encoded byte, :769)
+template <int NX, int NY, int NZ, int KIND, bool U8, bool TRC = false>
+DSP_HD void block_store_x(const BlockGeom &a, const TinyArgs &tx, float *out, uint8_t *out8, double mul8, const float *lds, long long bout, int cnt, int tid, const BlockTrc *t = nullptr)
 {
 	const int lines = NZ * NY * cnt;
 	for (int l = tid; l < lines; l += BLOCK_THREADS) {
@@ -135,7 +143,12 @@ DSP_HD void block_store_x(const BlockGeom &a, const TinyArgs &tx, float *out, ui
 			for (int j = 0; j < NX / 4; j++) {
 				uint32_t w4 = 0;
 #pragma unroll
-				for (int k = 0; k < 4; k++) w4 |= quantise_u8_of(o[4 * j + k], mul8, (float)mul8) << (8 * k);
+				for (int k = 0; k < 4; k++) {
+					if constexpr (TRC) {
+						if (t->thr) { const double pel = (double)o[4 * j + k] * mul8; w4 |= trc_u8_byte_from(t->thr, pel, trc_u8_seed(t->tp, pel)) << (8 * k); continue; }
+					}
+					w4 |= quantise_u8_of(o[4 * j + k], mul8, (float)mul8) << (8 * k);
+				}
 				__builtin_memcpy(out8 + off + 4 * j, &w4, 4);
 			}
 		} else {

@@ -14,6 +14,7 @@
 // Everything is a template over the sample type: float (the image tools) and double (the fftw_ API of spec / zoom's default build).
 // Phases are barrier-separated and numbered 0 .. NS+1 (load/pre, NS FFT stages, post/unpack).
 #pragma once
+#include "trc_u8_core.h"
 #include "dct_core.h"
 #include "elementwise_core.h"
 #include "spec_list.h"
@@ -245,6 +246,10 @@ template <class Re> DSP_HD void storev_a(const PassArgsT<Re> &a, long long off, 
 // planar (C = 1) row passes: `in` replaces the float input of a REDFT10 pass, `out` receives
 // quantise_u8(value * mul) instead of the float output of a REDFT01 pass.  Offsets are the plan's element offsets.
 struct U8IO { const uint8_t *in; uint8_t *out; double mul; };
+// motion --linear (dspfft_plan_set_u8_trc): what the kernels instantiated with TRC take instead (spec_inst_row_trc.hip; the phases reach it
+// through their U8IO pointer).  tab_in's decode table replaces the byte -> float conversion, tab_out's threshold table the quantiser
+// (trc_u8_core.h); trc_out is the id behind tab_out.  The plain kernels' argument stays the 24 bytes it was.
+struct U8IOTrc : U8IO { const TrcU8Tab *tab_in = nullptr, *tab_out = nullptr; int trc_out = 0; };
 
 // =================================================================================================
 // GS_ = distance in samples between consecutive pixels of the line in global memory.  GS_ == C_: the line's C_ interleaved channels all
@@ -316,7 +321,8 @@ struct RowSpecG {
 		else if (zf) prefetch_m<KIND, false, true>(a, bin, tid, st, io, zf, ch);       // zf: this line's tile flags (PassGeom::zflags)
 		else prefetch_m<KIND, false, false>(a, bin, tid, st, io, nullptr, ch);
 	}
-	template <int KIND, bool MASKED, bool FLAGGED, class ST>
+	// TRC (8-bit REDFT10 lines): the four bytes stay packed in pre[4 i] until phase 0 has the decode table to look them up in
+	template <int KIND, bool MASKED, bool FLAGGED, bool TRC = false, class ST>
 	static DSP_HD void prefetch_m(const PA &a, long long bin, int tid, ST &st, const U8IO *io, const uint8_t *zf, int ch = 0)
 	{
 		static_for<0, K_ROUNDS>([&](auto i) {
@@ -348,7 +354,8 @@ struct RowSpecG {
 					if ((i + 1) * T <= N / 4 || g < N / 4) {
 						uint32_t w4;
 						__builtin_memcpy(&w4, io->in + bin + 4 * g, 4);
-						static_for<0, 4>([&](auto q) { st.pre[i * 4 + q] = (Re)((w4 >> (8 * q)) & 0xffu); });
+						if constexpr (TRC) __builtin_memcpy(&st.pre[i * 4], &w4, 4);
+						else static_for<0, 4>([&](auto q) { st.pre[i * 4 + q] = (Re)((w4 >> (8 * q)) & 0xffu); });
 					}
 				});
 				return;
@@ -479,7 +486,8 @@ struct RowSpecG {
 
 	// phase 0 consumes the prefetched registers; phases 1.. work on LDS; the last one stores to `bout`
 	// STW: st.stw holds the stages' twiddles (the caller ran fetch_stage_twiddles)
-	template <int KIND, int PH, class ST, bool SEQTW = false, bool STW = false>
+	// TRC: io points at a U8IOTrc and the 8-bit ends go through its tables
+	template <int KIND, int PH, class ST, bool SEQTW = false, bool STW = false, bool TRC = false>
 	static DSP_HD void phase(const PA &a, CX *planes, long long bout, int tid, ST &st, const U8IO *io = nullptr)
 	{
 		Re *pf = reinterpret_cast<Re *>(planes);
@@ -492,6 +500,12 @@ struct RowSpecG {
 					static_for<0, U8_ROUNDS>([&](auto i) {
 						const int g = tid + i * T;
 						if ((i + 1) * T <= N / 4 || g < N / 4) {
+							if constexpr (TRC) {
+								uint32_t w4;
+								__builtin_memcpy(&w4, &st.pre[i * 4], 4);
+								const float *lut = static_cast<const U8IOTrc *>(io)->tab_in->lut;
+								static_for<0, 4>([&](auto q) { st.pre[i * 4 + q] = (Re)lut[(w4 >> (8 * q)) & 0xffu]; });
+							}
 							Re v0 = st.pre[i * 4];
 							if constexpr (i == 0) { if (g == 0) v0 *= a.in_scale0; }
 							planes[padded(g)] = cmk<Re>(v0, st.pre[i * 4 + 2]);
@@ -589,7 +603,11 @@ struct RowSpecG {
 							uint32_t w4 = 0;
 							static_for<0, 4>([&](auto q) {
 								const Re sc = (q == 0 && g == 0) ? a.scale * a.out_scale0 : a.scale;
-								w4 |= quantise_u8_of(f[q] * sc, io->mul, mulf) << (8 * q);
+								if constexpr (TRC) {
+									const double pel = (double)(f[q] * sc) * io->mul;
+									const U8IOTrc *it = static_cast<const U8IOTrc *>(io);
+									w4 |= trc_u8_byte_from(it->tab_out->thr, pel, trc_u8_seed(trc_params(it->trc_out), pel)) << (8 * q);
+								} else w4 |= quantise_u8_of(f[q] * sc, io->mul, mulf) << (8 * q);
 							});
 							__builtin_memcpy(io->out + bout + 4 * g, &w4, 4);
 						});

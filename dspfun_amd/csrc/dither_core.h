@@ -1,4 +1,5 @@
-// dither_core.h -- motion's Floyd-Steinberg 8-bit store (motion/motion.c:756-788 with -d: spec none, 8-bit pixels, !linear) as the
+// dither_core.h -- motion's Floyd-Steinberg 8-bit store (motion/motion.c:756-788 with -d: spec none, 8-bit pixels; TRC = true: --linear,
+// the byte is the encoded one, trc_u8_core.h, while the error stays the reference's c - byte / (normalization^2 scalefactor), :780) as the
 // arithmetic of ONE pixel, shared by the HIP kernels (motion_dither.hip) and host code (the CPU tests compile it with g++).
 //
 // The reference walks a plane in raster order and adds each pixel's error into four float neighbours.  Every `+=` rounds back to float
@@ -14,6 +15,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "radix.h"
+#include "trc_u8_core.h"
 
 #if defined(__clang__)
 #define DITHER_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -44,8 +46,10 @@ DSP_HD float dither_add(float c, double term)
 
 // One pixel.  c: the inverse transform's float; up: the row above exists; xm / xp: columns x-1 / x+1 exist; dm, d0, dq: dp of the pixels
 // (y-1, x-1), (y-1, x), (y-1, x+1); dl: dp of (y, x-1).  Returns the byte (motion.c:759-776) and its error in dp (:778).
+// TRC: thr is the function's threshold table and tp its parameters (they only seed the search in thr).
+template <bool TRC = false>
 DSP_HD uint8_t dither_pel(float c, bool up, bool xm, bool xp, double dm, double d0, double dq, double dl, double scalefactor, double norm,
-                          const double *tab, double &dp)
+                          const double *tab, double &dp, const double *thr = nullptr, const TrcParams *tp = nullptr)
 {
 	DITHER_NO_CONTRACT
 	if (up) {
@@ -56,15 +60,18 @@ DSP_HD uint8_t dither_pel(float c, bool up, bool xm, bool xp, double dm, double 
 	if (xm) c = dither_add(c, dl * 7 / 16);
 	double pel = (double)c * scalefactor * norm;
 	pel *= norm;
-	const uint8_t p = pel > 255 ? 255 : pel < 0 ? 0 : (uint8_t)round(pel);     // lround: halves away from zero
+	uint8_t p;
+	if constexpr (TRC) p = (uint8_t)trc_u8_byte_from(thr, pel, trc_u8_seed(*tp, pel));   // :769,776
+	else p = pel > 255 ? 255 : pel < 0 ? 0 : (uint8_t)round(pel);              // lround: halves away from zero
 	dp = (double)c - tab[p];
 	return p;
 }
 
 // One h x w plane in raster order, as the reference walks it.  dprow: w doubles of scratch at stride dstride (the previous row's errors,
 // overwritten as the row advances); in and out are addressed (y * pitch + x).
+template <bool TRC = false>
 DSP_HD void dither_plane_serial(uint8_t *out, const float *in, long long pitch, int h, int w, double scalefactor, double norm, const double *tab,
-                                double *dprow, int dstride)
+                                double *dprow, int dstride, const double *thr = nullptr, const TrcParams *tp = nullptr)
 {
 	for (int y = 0; y < h; y++) {
 		const bool up = y > 0;
@@ -74,7 +81,7 @@ DSP_HD void dither_plane_serial(uint8_t *out, const float *in, long long pitch, 
 			const bool xp = x + 1 < w;
 			dq = (up && xp) ? dprow[(long long)(x + 1) * dstride] : 0.0;
 			double dp;
-			out[(long long)y * pitch + x] = dither_pel(in[(long long)y * pitch + x], up, x > 0, xp, dm, d0, dq, dl, scalefactor, norm, tab, dp);
+			out[(long long)y * pitch + x] = dither_pel<TRC>(in[(long long)y * pitch + x], up, x > 0, xp, dm, d0, dq, dl, scalefactor, norm, tab, dp, thr, tp);
 			if (x > 0) dprow[(long long)(x - 1) * dstride] = dl;       // (y-1, x-1) is not read again in this row
 			dl = dp;
 		}

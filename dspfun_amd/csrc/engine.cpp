@@ -28,6 +28,8 @@
 #include "zoom_anim_core.h"
 #include "trc_core.h"
 #include "topn_core.h"
+#include "block_rt.h"
+#include "trc_u8_core.h"
 
 using namespace dspfft;
 
@@ -52,6 +54,15 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_topn_blocks_la
                                                                                       void *d_work, size_t work_bytes, int restore_dc, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) size_t dspfft_topn_blocks_bytes(size_t count, size_t nblocks);
 extern "C" __attribute__((weak)) const char *dspfft_motion_last_error(void);
+// motion --linear on 8-bit samples (dspfft_plan_set_u8_trc and the stand-alone calls): motion_ops.hip's flat and region kernels,
+// motion_dither.hip's dithered store, block_trc.hip's fused block roundtrip and spec_inst_row_trc.hip's row ends.  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_u8_trc_flat_launch(void *d_dst, const void *d_src, double mul, uint64_t len, int store, int trc, const void *tab, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_u8_trc_region_launch(void *d_dst, const void *d_src, const int n[3], const long long sdst[3], const long long ssrc[3], int store,
+                                                                                        double m0, double m1, double m2, int trc, const void *tab, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_trc_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor,
+                                                                                     double normalization, int trc, const void *tab, void *stream, char *err, size_t errlen);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_trc_launch(const dspfft::BlockRtTrcArgs *a, int nwg, size_t lds, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_row_u8_trc_launch(int row_spec_id, const dspfft::PassArgs *a, const dspfft::U8IOTrc *io, int nwg, void *stream);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -251,6 +262,11 @@ struct dspfft_plan_s {
 	const void *mod_table = nullptr;
 	bool first_axis_first = false;           // pass order (dspfft_plan_many_r2r_ordered): what a slice plan of this plan is built with
 	int col_kpref = 0;                       // column tile width asked of be_find_spec first (slice plans: the narrow tile, see RtSlices)
+	// dspfft_plan_set_u8_trc: the transfer characteristic of this plan's 8-bit end and its tables on the device (a TrcU8Tab; a slice plan
+	// borrows its parent's)
+	int u8_trc = 0;
+	void *u8_tab = nullptr;
+	bool u8_tab_owned = false;
 	// dspfft_execute_roundtrip_u8 over a clip of frames: plans for a slice of the clip whose float intermediate the Infinity Cache holds
 	// (roundtrip_core), built on first use and owned by the forward plan
 	struct RtSlices {
@@ -1685,8 +1701,20 @@ int run_pass_u8(const dspfft_plan_s *pl, const Pass &P, const float *in, float *
 	return 0;
 }
 
+// the same pass through the listed kernel that has a transfer characteristic's table at its 8-bit end (rt_check has seen to it that the pass
+// has a listed kernel and that the launcher is there)
+int run_pass_u8_trc(const dspfft_plan_s *pl, const Pass &P, const float *in, float *out, bool last, const U8IOTrc &io, void *stream)
+{
+	PassArgs a;
+	fill_args(a, P.spa, pl, P, in, out, last ? pl->scale : 1.0, Fuse());
+	if (int rc = dspfft_row_u8_trc_launch(P.spec.id, &a, &io, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8 with a transfer characteristic): backend code %d", P.desc.c_str(), rc);
+	return 0;
+}
+
 // motion's -d (dspfft_execute_roundtrip_u8_dither): the bytes come from the dither kernel (motion_dither.hip) instead of the last inverse pass
 struct Dither { uint8_t *out8; double sf, norm; };
+// the transfer characteristic of one 8-bit end of a roundtrip call (id = 0: none) and its tables on the device
+struct U8Trc { int id = 0; const void *tab = nullptr; };
 // the planes of a plan's output layout: its last two axes (rank 1: rows of their own), the first of three and the batch axes index planes
 int dither_geom_of(const dspfft_plan_s *p, dspfft_dither_geom &g)
 {
@@ -1704,13 +1732,14 @@ int dither_geom_of(const dspfft_plan_s *p, dspfft_dither_geom &g)
 	}
 	return 0;
 }
-int dither_store(const dspfft_plan_s *inv, const float *work, const Dither &dz, void *stream)
+int dither_store(const dspfft_plan_s *inv, const float *work, const Dither &dz, const U8Trc &trc, void *stream)
 {
 	dspfft_dither_geom g;
 	if (int rc = dither_geom_of(inv, g)) return rc;
 	char err[256] = "";
 	if (!dspfft_dither_launch) return fail(-3, "dithered 8-bit store: not in this build");
-	if (dspfft_dither_launch(dz.out8, work, &g, dz.sf, dz.norm, stream, err, sizeof err)) return fail(-4, "%s", err);
+	if (trc.id ? dspfft_dither_trc_launch(dz.out8, work, &g, dz.sf, dz.norm, trc.id, trc.tab, stream, err, sizeof err)
+	           : dspfft_dither_launch(dz.out8, work, &g, dz.sf, dz.norm, stream, err, sizeof err)) return fail(-4, "%s", err);
 	return 0;
 }
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
@@ -1763,7 +1792,18 @@ struct RtCall {
 	long long sw3[3], si3[3];
 	MotionFilter mf;
 	TopnRuns runs;                        // keep != 0 and not `block`: the blocks as contiguous runs of the working buffer
+	U8Trc trc_in, trc_out;                // dspfft_plan_set_u8_trc of the forward plan (8-bit input) and of the inverse plan (8-bit or dithered output)
+	bool dithered;                        // set by roundtrip_core before rt_check: the bytes come from the dither kernel
 };
+// the conversions at the ends of the unfused paths, plain or through the call's transfer characteristic
+int rt_u8_in(const RtCall &c, float *dst, uint64_t len)
+{
+	return c.trc_in.id ? dspfft_u8_trc_flat_launch(dst, c.d_in8, 1.0, len, 0, c.trc_in.id, c.trc_in.tab, c.stream) : be_u8_to_f32(dst, c.d_in8, len, c.stream);
+}
+int rt_u8_out(const RtCall &c, const float *src, uint64_t len)
+{
+	return c.trc_out.id ? dspfft_u8_trc_flat_launch(c.d_out8, src, c.mul8, len, 1, c.trc_out.id, c.trc_out.tab, c.stream) : be_f32_to_u8(c.d_out8, src, c.mul8, len, c.stream);
+}
 
 // every rejection of a roundtrip call; nothing has been launched when it returns
 int rt_check(RtCall &c)
@@ -1812,6 +1852,18 @@ int rt_check(RtCall &c)
 	c.block = !c.rescale && block_roundtrip_ok(fwd, inv) && !((c.d_in8 ? 3u : 15u) & pin) && !((c.d_out8 ? 3u : 15u) & pout);
 	c.u8_first = pass_has_u8(fwd, fwd->passes[0]);
 	c.u8_last = pass_has_u8(inv, inv->passes[ni - 1]);
+	// motion --linear: a plan's transfer characteristic acts where the call has an 8-bit end for it
+	if (c.d_in8 && fwd->u8_trc) c.trc_in = U8Trc{fwd->u8_trc, fwd->u8_tab};
+	if ((c.d_out8 || c.dithered) && inv->u8_trc) c.trc_out = U8Trc{inv->u8_trc, inv->u8_tab};
+	if (c.trc_in.id || c.trc_out.id) {
+		if (!dspfft_u8_trc_flat_launch || !dspfft_u8_trc_region_launch || !dspfft_dither_trc_launch || !dspfft_block_trc_launch || !dspfft_row_u8_trc_launch)
+			return fail(-3, "8-bit roundtrip with a transfer characteristic: not built into this library (the kernels are HIP-only)");
+		// the fused ends with tables: the block kernel where the tables fit behind its tile, the listed row kernels (a row kernel compiled at
+		// plan time has no such twin: that end is converted by a sweep)
+		c.block = c.block && fwd->blk_lds % 16 == 0 && fwd->blk_lds + sizeof(TrcU8Tab) <= 64 * 1024;
+		if (c.trc_in.id) c.u8_first = c.u8_first && fwd->passes[0].has_spec && be_spec_has_u8(fwd->passes[0].spec.id);
+		if (c.trc_out.id) c.u8_last = c.u8_last && inv->passes[ni - 1].has_spec && be_spec_has_u8(inv->passes[ni - 1].spec.id);
+	}
 	if (c.keep) {
 		// --coeff-limit: at or above the block's embedding count nothing is dropped (motion.c:654-657) and the call is the plain one
 		const bool runs = topn_runs_of(fwd, inv, c.runs);
@@ -1855,6 +1907,14 @@ int rt_run_block(const RtCall &c)
 	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
 	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
 	a.filt = c.mf; a.coded = c.coded;
+	if (c.trc_in.id || c.trc_out.id) {
+		BlockRtTrcArgs t;
+		static_cast<BlockRtArgs &>(t) = a;
+		t.keep = (unsigned int)c.keep;
+		t.tab_in = (const TrcU8Tab *)c.trc_in.tab; t.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; t.trc_out = c.trc_out.id;
+		if (int rc = dspfft_block_trc_launch(&t, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip with a transfer characteristic): backend code %d", rc);
+		return 0;
+	}
 	if (c.keep) {
 		BlockRtTopnArgs t;
 		static_cast<BlockRtArgs &>(t) = a;
@@ -1883,7 +1943,9 @@ int rt_run_rescale(const RtCall &c)
 	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
 	float *const d_out = c.d_out;
 	if (c.d_in8) {
-		if (be_zero(d_out, (size_t)c.span * sizeof(float), c.stream) || be_region_u8_to_f32(d_out, c.d_in8, c.nf3, c.sw3, c.si3, c.stream)) return fail(-4, "launch failed");
+		if (be_zero(d_out, (size_t)c.span * sizeof(float), c.stream) ||
+		    (c.trc_in.id ? dspfft_u8_trc_region_launch(d_out, c.d_in8, c.nf3, c.sw3, c.si3, 0, 1.0, 1.0, 1.0, c.trc_in.id, c.trc_in.tab, c.stream)
+		                 : be_region_u8_to_f32(d_out, c.d_in8, c.nf3, c.sw3, c.si3, c.stream))) return fail(-4, "launch failed");
 	} else if (c.d_in != d_out) {
 		if (be_zero(d_out, (size_t)c.span * sizeof(float), c.stream)) return fail(-4, "launch failed");
 	}
@@ -1895,7 +1957,8 @@ int rt_run_rescale(const RtCall &c)
 	if (c.fp && be_motion_filter(d_out, c.mf, (uint64_t)c.span, c.coded, c.stream)) return fail(-4, "filter launch failed");
 	for (size_t i = 0; i < ni; i++)
 		if (int rc = run_pass<float>(inv, inv->passes[i], (const float *)d_out, d_out, i + 1 == ni, c.stream)) return rc;
-	if (c.d_out8 && be_region_f32_to_u8(c.d_out8, d_out, c.mul8, c.ni3, c.sw3, c.sw3, c.stream)) return fail(-4, "launch failed");
+	if (c.d_out8 && (c.trc_out.id ? dspfft_u8_trc_region_launch(c.d_out8, d_out, c.ni3, c.sw3, c.sw3, 1, c.mul8, 1.0, 1.0, c.trc_out.id, c.trc_out.tab, c.stream)
+	                              : be_region_f32_to_u8(c.d_out8, d_out, c.mul8, c.ni3, c.sw3, c.sw3, c.stream))) return fail(-4, "launch failed");
 	return 0;
 }
 
@@ -1908,13 +1971,16 @@ int rt_run_passes(const RtCall &c)
 	float *const d_out = c.d_out;
 	void *const stream = c.stream;
 	const bool sweep_in = c.d_in8 && !c.u8_first;        // no fused load: one sweep
-	if (sweep_in && be_u8_to_f32(d_out, c.d_in8, (uint64_t)c.span, stream)) return fail(-4, "launch failed");
+	if (sweep_in && rt_u8_in(c, d_out, (uint64_t)c.span)) return fail(-4, "launch failed");
 	const float *d_in = sweep_in ? d_out : c.d_in;
 	for (size_t i = 0; i + 1 < nf; i++) {
 		const Pass &P = fwd->passes[i];
 		if (i == 0 && c.d_in8 && c.u8_first) {
 			U8IO io; io.in = c.d_in8; io.out = nullptr; io.mul = 1.0;
-			if (int rc = run_pass_u8(fwd, P, d_out, d_out, false, io, stream)) return rc;
+			if (c.trc_in.id) {
+				U8IOTrc t; static_cast<U8IO &>(t) = io; t.tab_in = (const TrcU8Tab *)c.trc_in.tab;
+				if (int rc = run_pass_u8_trc(fwd, P, d_out, d_out, false, t, stream)) return rc;
+			} else if (int rc = run_pass_u8(fwd, P, d_out, d_out, false, io, stream)) return rc;
 			continue;
 		}
 		if (int rc = run_pass<float>(fwd, P, P.first ? d_in : d_out, d_out, false, stream)) return rc;
@@ -1946,12 +2012,15 @@ int rt_run_passes(const RtCall &c)
 		const Pass &P = inv->passes[i];
 		if (i + 1 == ni && c.d_out8 && c.u8_last) {
 			U8IO io; io.in = nullptr; io.out = c.d_out8; io.mul = c.mul8;
-			if (int rc = run_pass_u8(inv, P, d_out, d_out, true, io, stream)) return rc;
+			if (c.trc_out.id) {
+				U8IOTrc t; static_cast<U8IO &>(t) = io; t.tab_out = (const TrcU8Tab *)c.trc_out.tab; t.trc_out = c.trc_out.id;
+				if (int rc = run_pass_u8_trc(inv, P, d_out, d_out, true, t, stream)) return rc;
+			} else if (int rc = run_pass_u8(inv, P, d_out, d_out, true, io, stream)) return rc;
 			continue;
 		}
 		if (int rc = run_pass<float>(inv, P, (const float *)d_out, d_out, i + 1 == ni, stream)) return rc;
 	}
-	if (c.d_out8 && !c.u8_last && be_f32_to_u8(c.d_out8, d_out, c.mul8, (uint64_t)c.span, stream)) return fail(-4, "launch failed");    // no fused store: one sweep
+	if (c.d_out8 && !c.u8_last && rt_u8_out(c, d_out, (uint64_t)c.span)) return fail(-4, "launch failed");    // no fused store: one sweep
 	return 0;
 }
 
@@ -2022,6 +2091,11 @@ void follow_scales(std::initializer_list<dspfft_plan_s *> slices, const dspfft_p
 {
 	for (dspfft_plan_s *q : slices) if (q) { q->scale = of->scale; for (int a = 0; a < 2; a++) { q->in0[a] = of->in0[a]; q->out0[a] = of->out0[a]; } }
 }
+// ... and its transfer characteristic (dspfft_plan_set_u8_trc); the tables stay the parent's
+void follow_trc(std::initializer_list<dspfft_plan_s *> slices, const dspfft_plan_s *of)
+{
+	for (dspfft_plan_s *q : slices) if (q) { q->u8_trc = of->u8_trc; q->u8_tab = of->u8_tab; }
+}
 // From the fork on, the join of the library's stream: on every way out of roundtrip_sliced the caller's stream waits for what the side stream
 // was given, so that nothing of this call writes the caller's buffers once the caller's stream is through.  (Sets no error text: the first
 // error's stays.)
@@ -2065,6 +2139,8 @@ int roundtrip_sliced(const RtCall &c, const Dither *dither)
 	}
 	follow_scales({r->fwd, r->fwd_rem}, fwd);
 	follow_scales({r->inv, r->inv_rem}, inv);
+	follow_trc({r->fwd, r->fwd_rem}, fwd);
+	follow_trc({r->inv, r->inv_rem}, inv);
 	const long long fin = fwd->batches[0].is, fwk = fwd->batches[0].os, fout = inv->batches[0].os;
 	const bool two = r->side != nullptr;
 	if (two && (be_event_record(r->ev_fork, c.stream) || be_stream_wait_event(r->side, r->ev_fork))) return fail(-4, "stream fork failed");
@@ -2087,6 +2163,7 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
                    size_t keep, void *topn_work, size_t topn_work_bytes)
 {
 	RtCall c = {fwd, inv, d_in, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream, keep, topn_work, topn_work_bytes};
+	c.dithered = dither != nullptr;
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
 	if (c.block) rc = rt_run_block(c);
@@ -2098,7 +2175,7 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 		rc = rt_run_passes(c);
 	}
 	if (rc || !dither) return rc;
-	return dither_store(inv, d_out, *dither, stream);
+	return dither_store(inv, d_out, *dither, c.trc_out, stream);
 }
 }  // namespace
 
@@ -2302,6 +2379,7 @@ extern "C" void dspfft_destroy_plan(dspfft_plan pl)
 	for (Pass &P : pl->passes) P.tab.release();
 	for (Pass &P : pl->split) P.tab.release();
 	be_free(pl->zflags); be_free(pl->zpage); be_free(pl->zranges); be_free(pl->eids);
+	if (pl->u8_tab_owned) be_free(pl->u8_tab);
 	delete pl;
 }
 
@@ -2313,6 +2391,7 @@ extern "C" int dspfft_plan_describe(dspfft_plan pl, char *buf, size_t buflen)
 	for (const Pass &P : pl->split) { s += P.desc; s += "\n"; }
 	if (pl->has_block) { s += pl->blk_desc; s += "\n"; }
 	for (const Pass &P : pl->passes) { if (!pl->split.empty() || pl->has_block) s += "plain "; s += P.desc; if (!P.hostloop.empty()) s += " +hostloop"; s += "\n"; }
+	if (pl->u8_trc) { s += "8-bit end of a roundtrip through transfer characteristic "; s += trc_name(pl->u8_trc); s += "\n"; }
 	std::lock_guard<std::mutex> lock(pl->rt_mutex);                  // (another thread's first roundtrip over a clip may be adding to rt_slices)
 	for (const auto &r : pl->rt_slices) {                            // (present once dspfft_execute_roundtrip_u8 has walked a clip in slices)
 		char b[256];
@@ -2446,6 +2525,64 @@ extern "C" int dspfft_f32_to_u8(uint8_t *d, const float *src, double mul, uint64
 {
 	if (!d || !src) return fail(-1, "bad arguments");
 	return be_f32_to_u8(d, src, mul, len, s) ? fail(-4, "launch failed") : 0;
+}
+
+// ---- motion --linear on 8-bit samples (include/dspfft.h; trc_u8_core.h; kernels in motion_ops.hip and the units named at the weak references) ----
+extern "C" int dspfft_plan_set_u8_trc(dspfft_plan pl, int trc)
+{
+	if (!pl) return fail(-1, "null plan");
+	if (trc == 0) {                      // back to the plain conversions; the tables go with the plan, or with the next function
+		pl->u8_trc = 0;
+		return 0;
+	}
+	if (pl->f64) return fail(-1, "8-bit transfer characteristic: the 8-bit roundtrip takes f32 plans");
+	if (!trc_built(trc)) return fail(-1, "8-bit transfer characteristic %d is not built", trc);
+	if (!dspfft_u8_trc_flat_launch || !dspfft_u8_trc_region_launch || !dspfft_dither_trc_launch || !dspfft_block_trc_launch || !dspfft_row_u8_trc_launch)
+		return fail(-3, "8-bit transfer characteristic: not in this build (the kernels are HIP-only)");
+	if (pl->u8_trc == trc) return 0;
+	// fresh memory for another function's tables: a roundtrip enqueued earlier may still be reading the old ones (be_free waits for it)
+	auto host = std::make_unique<TrcU8Tab>();
+	trc_u8_tab_build(*host, trc);
+	void *d = be_alloc(sizeof(TrcU8Tab));
+	if (!d || be_upload(d, host.get(), sizeof(TrcU8Tab))) { be_free(d); return fail(-4, "8-bit transfer characteristic: table upload failed"); }
+	if (pl->u8_tab_owned) be_free(pl->u8_tab);
+	pl->u8_tab = d; pl->u8_tab_owned = true; pl->u8_trc = trc;
+	return 0;
+}
+namespace {
+int u8_trc_args(const void *dst, const void *src, int trc)
+{
+	if (!dst || !src) return fail(-1, "8-bit transfer characteristic: null buffer");
+	if (!trc_built(trc)) return fail(-1, "8-bit transfer characteristic %d is not built", trc);
+	if (!dspfft_u8_trc_flat_launch || !dspfft_u8_trc_region_launch) return fail(-3, "8-bit transfer characteristic: not in this build (the kernels are HIP-only, motion_ops.hip)");
+	return 0;
+}
+int motion_u8_linear(void *d_dst, const void *d_src, const int n[3], const int minbuf_hw[2], int store, double scalefactor, double normalization, int trc, void *stream)
+{
+	if (!d_dst || !d_src || !n || !minbuf_hw || n[0] < 1 || n[1] < 1 || n[2] < 1 || minbuf_hw[0] < n[1] || minbuf_hw[1] < n[2]) return fail(-1, "motion --linear: bad arguments");
+	if (int rc = u8_trc_args(d_dst, d_src, trc)) return rc;
+	const long long st[3] = {(long long)minbuf_hw[0] * minbuf_hw[1], minbuf_hw[1], 1};
+	return dspfft_u8_trc_region_launch(d_dst, d_src, n, st, st, store, scalefactor, normalization, normalization, trc, nullptr, stream) ? fail(-4, "motion --linear: kernel launch failed") : 0;
+}
+}  // namespace
+extern "C" int dspfft_u8_to_f32_trc(float *d_dst, const uint8_t *d_src, uint64_t len, int trc, void *stream)
+{
+	if (int rc = u8_trc_args(d_dst, d_src, trc)) return rc;
+	return dspfft_u8_trc_flat_launch(d_dst, d_src, 1.0, len, 0, trc, nullptr, stream) ? fail(-4, "8-bit transfer characteristic: kernel launch failed") : 0;
+}
+extern "C" int dspfft_f32_to_u8_trc(uint8_t *d_dst, const float *d_src, double mul, uint64_t len, int trc, void *stream)
+{
+	if (int rc = u8_trc_args(d_dst, d_src, trc)) return rc;
+	return dspfft_u8_trc_flat_launch(d_dst, d_src, mul, len, 1, trc, nullptr, stream) ? fail(-4, "8-bit transfer characteristic: kernel launch failed") : 0;
+}
+extern "C" int dspfft_motion_load_u8_linear(float *d_coeffs, const uint8_t *d_pix, const int n[3], const int minbuf_hw[2], int trc, void *stream)
+{
+	return motion_u8_linear(d_coeffs, d_pix, n, minbuf_hw, 0, 1.0, 1.0, trc, stream);
+}
+extern "C" int dspfft_motion_store_u8_linear(uint8_t *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], double scalefactor, double normalization,
+                                             int trc, void *stream)
+{
+	return motion_u8_linear(d_pix, d_coeffs, n, minbuf_hw, 1, scalefactor, normalization, trc, stream);
 }
 
 // ---- transfer characteristics (include/dspfft.h; trc_core.h; kernels in pointwise.hip and motion_ops.hip) ----

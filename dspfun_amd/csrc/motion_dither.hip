@@ -24,6 +24,7 @@
 using namespace dspfft;
 
 extern "C" int dspfft_motion_set_error(const char *m);     // motion_ops.hip: the message dspfft_motion_last_error returns
+extern "C" const void *dspfft_u8_trc_cached_tab(int trc);  // motion_ops.hip: this device's tables of a transfer characteristic (NULL: upload failed)
 
 namespace {
 
@@ -47,28 +48,47 @@ __device__ inline long long plane_base(const Geom &g, long long p)
 	return b0 * g.step[0] + b1 * g.step[1] + b2 * g.step[2] + z * g.plane;
 }
 
+// --linear (TRC): the function's 256 thresholds lie in LDS behind the error table, and the rings / row errors behind them
+struct TrcArg { const TrcU8Tab *tab; int id; };
+constexpr int kTrcDoubles = 256;
+
 // one lane per plane; 64 lanes per workgroup, their previous-row errors interleaved in LDS (lane-major: no bank conflicts)
-__global__ __launch_bounds__(64) void dither_serial_kernel(uint8_t *pix, const float *co, Geom g, long long nplanes, double sf, double norm)
+template <bool TRC>
+__device__ __forceinline__ void dither_serial_body(uint8_t *pix, const float *co, Geom g, long long nplanes, double sf, double norm, TrcArg t)
 {
 	extern __shared__ double lds[];
-	double *tab = lds, *dprow = lds + 256;
-	for (int i = threadIdx.x; i < 256; i += blockDim.x) tab[i] = dither_table_entry(i, sf, norm);
+	double *tab = lds, *thr = lds + 256, *dprow = lds + 256 + (TRC ? kTrcDoubles : 0);
+	for (int i = threadIdx.x; i < 256; i += blockDim.x) { tab[i] = dither_table_entry(i, sf, norm); if constexpr (TRC) thr[i] = t.tab->thr[i]; }
 	__syncthreads();
 	const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (p >= nplanes) return;
 	const long long base = plane_base(g, p);
-	dither_plane_serial(pix + base, co + base, g.row, g.h, g.w, sf, norm, tab, dprow + threadIdx.x, blockDim.x);
+	if constexpr (TRC) {
+		const TrcParams tp = trc_params(t.id);
+		dither_plane_serial<true>(pix + base, co + base, g.row, g.h, g.w, sf, norm, tab, dprow + threadIdx.x, blockDim.x, thr, &tp);
+	} else dither_plane_serial(pix + base, co + base, g.row, g.h, g.w, sf, norm, tab, dprow + threadIdx.x, blockDim.x);
+}
+__global__ __launch_bounds__(64) void dither_serial_kernel(uint8_t *pix, const float *co, Geom g, long long nplanes, double sf, double norm)
+{
+	dither_serial_body<false>(pix, co, g, nplanes, sf, norm, TrcArg{nullptr, 0});
+}
+__global__ __launch_bounds__(64) void dither_serial_trc_kernel(uint8_t *pix, const float *co, Geom g, long long nplanes, double sf, double norm, TrcArg t)
+{
+	dither_serial_body<true>(pix, co, g, nplanes, sf, norm, t);
 }
 
 struct WaveSched { int nw, D, R, L; };   // waves, band-to-band offset, ring length, steps per band (a multiple of kChunk)
 
-__global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_kernel(uint8_t *pix, const float *co, Geom g, WaveSched s, double sf, double norm)
+template <bool TRC>
+__device__ __forceinline__ void dither_wave_body(uint8_t *pix, const float *co, Geom g, WaveSched s, double sf, double norm, TrcArg t)
 {
 	extern __shared__ double lds[];
-	double *tab = lds, *rings = lds + 256;
+	double *tab = lds, *thr = lds + 256, *rings = lds + 256 + (TRC ? kTrcDoubles : 0);
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	for (int i = threadIdx.x; i < 256; i += blockDim.x) tab[i] = dither_table_entry(i, sf, norm);
+	for (int i = threadIdx.x; i < 256; i += blockDim.x) { tab[i] = dither_table_entry(i, sf, norm); if constexpr (TRC) thr[i] = t.tab->thr[i]; }
 	__syncthreads();
+	TrcParams tp;
+	if constexpr (TRC) tp = trc_params(t.id);
 	const long long base = plane_base(g, blockIdx.x);
 	const int h = g.h, w = g.w, nbands = (h + 63) >> 6;
 	const long long total = (long long)(nbands - 1) * s.D + s.L;
@@ -123,7 +143,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_kernel(uint8_t *pi
 				a = b0; b0 = c; c = nxt;
 				const bool act = rowok && x >= 0 && x < w;
 				double dp;
-				ob[i] = dither_pel(v[i], up, x > 0, x + 1 < w, a, b0, c, left, sf, norm, tab, dp);
+				ob[i] = dither_pel<TRC>(v[i], up, x > 0, x + 1 < w, a, b0, c, left, sf, norm, tab, dp, thr, &tp);
 				if (!act) dp = 0;
 				left = dp;
 				if (lane == 63 && act) ring_w[ws] = dp;
@@ -140,6 +160,14 @@ __global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_kernel(uint8_t *pi
 		}
 		__syncthreads();
 	}
+}
+__global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_kernel(uint8_t *pix, const float *co, Geom g, WaveSched s, double sf, double norm)
+{
+	dither_wave_body<false>(pix, co, g, s, sf, norm, TrcArg{nullptr, 0});
+}
+__global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_trc_kernel(uint8_t *pix, const float *co, Geom g, WaveSched s, double sf, double norm, TrcArg t)
+{
+	dither_wave_body<true>(pix, co, g, s, sf, norm, t);
 }
 
 bool small_plane(int h, int w) { return w <= 64 && (long long)h * w <= 1024; }
@@ -166,9 +194,9 @@ int dbad(char *err, size_t len, const char *m) { if (err && len) snprintf(err, l
 
 }  // namespace
 
-// The launcher behind both entry points (engine.cpp reaches it through a weak reference: absent from the CPU emulation build).
-extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp,
-                                                                           double scalefactor, double normalization, void *stream, char *err, size_t errlen)
+// trc = 0: the plain store; else tab points at the function's tables on the device
+static int dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp, double scalefactor, double normalization, int trc, const void *tab,
+                         void *stream, char *err, size_t errlen)
 {
 	if (!d_pix || !d_coeffs || !gp) return dbad(err, errlen, "dither: null pointer");
 	const dspfft_dither_geom &q = *gp;
@@ -182,25 +210,52 @@ extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_launch(uint8_
 	for (int i = 0; i < 3; i++) { g.nb[i] = q.nblocks[i]; g.step[i] = q.block_step[i]; }
 	const long long nplanes = (long long)g.d * g.nb[0] * g.nb[1] * g.nb[2];
 	hipStream_t st = (hipStream_t)stream;
+	const TrcArg ta = {(const TrcU8Tab *)tab, trc};
 	if (small_plane(g.h, g.w)) {
-		const size_t lds = (256 + 64 * (size_t)g.w) * sizeof(double);
+		const size_t lds = (256 + (trc ? kTrcDoubles : 0) + 64 * (size_t)g.w) * sizeof(double);
 		const long long nwg = (nplanes + 63) / 64;
 		if (nwg >= (1ll << 31)) return dbad(err, errlen, "dither: too many planes");
-		hipLaunchKernelGGL(dither_serial_kernel, dim3((unsigned)nwg), dim3(64), lds, st, d_pix, d_coeffs, g, nplanes, scalefactor, normalization);
+		if (trc) hipLaunchKernelGGL(dither_serial_trc_kernel, dim3((unsigned)nwg), dim3(64), lds, st, d_pix, d_coeffs, g, nplanes, scalefactor, normalization, ta);
+		else hipLaunchKernelGGL(dither_serial_kernel, dim3((unsigned)nwg), dim3(64), lds, st, d_pix, d_coeffs, g, nplanes, scalefactor, normalization);
 	} else {
 		const WaveSched s = wave_sched(g.h, g.w, wave_limit());
-		const size_t lds = (256 + (size_t)(s.nw + 1) * s.R) * sizeof(double);
+		const size_t lds = (256 + (trc ? kTrcDoubles : 0) + (size_t)(s.nw + 1) * s.R) * sizeof(double);
 		if (lds > kMaxLds) return dbad(err, errlen, "dither: plane too wide for the wavefront kernel's LDS rings (w above about 9000)");
 		if (nplanes >= (1ll << 31)) return dbad(err, errlen, "dither: too many planes");
-		hipLaunchKernelGGL(dither_wave_kernel, dim3((unsigned)nplanes), dim3(64 * s.nw), lds, st, d_pix, d_coeffs, g, s, scalefactor, normalization);
+		if (trc) hipLaunchKernelGGL(dither_wave_trc_kernel, dim3((unsigned)nplanes), dim3(64 * s.nw), lds, st, d_pix, d_coeffs, g, s, scalefactor, normalization, ta);
+		else hipLaunchKernelGGL(dither_wave_kernel, dim3((unsigned)nplanes), dim3(64 * s.nw), lds, st, d_pix, d_coeffs, g, s, scalefactor, normalization);
 	}
 	return hipGetLastError() == hipSuccess ? 0 : dbad(err, errlen, "dither: kernel launch failed");
+}
+
+// The launchers behind the entry points (engine.cpp reaches them through weak references: absent from the CPU emulation build).
+extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp,
+                                                                           double scalefactor, double normalization, void *stream, char *err, size_t errlen)
+{
+	return dither_launch(d_pix, d_coeffs, gp, scalefactor, normalization, 0, nullptr, stream, err, errlen);
+}
+// --linear: trc is a built id (engine.cpp has checked it); tab: a plan's device tables, or NULL for motion_ops.hip's own
+extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_trc_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp, double scalefactor,
+                                                                               double normalization, int trc, const void *tab, void *stream, char *err, size_t errlen)
+{
+	if (!tab) tab = dspfft_u8_trc_cached_tab(trc);
+	if (!tab) return dbad(err, errlen, "dither: the transfer characteristic's tables could not be uploaded");
+	return dither_launch(d_pix, d_coeffs, gp, scalefactor, normalization, trc, tab, stream, err, errlen);
 }
 
 extern "C" int dspfft_motion_dither_u8(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor, double normalization, void *stream)
 {
 	char err[256];
 	const int rc = dspfft_dither_launch(d_pix, d_coeffs, g, scalefactor, normalization, stream, err, sizeof err);
+	if (rc) dspfft_motion_set_error(err);
+	return rc;
+}
+
+extern "C" int dspfft_motion_dither_u8_trc(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor, double normalization, int trc, void *stream)
+{
+	if (!trc_built(trc)) { dspfft_motion_set_error("dither: the transfer characteristic is not built"); return -1; }
+	char err[256];
+	const int rc = dspfft_dither_trc_launch(d_pix, d_coeffs, g, scalefactor, normalization, trc, nullptr, stream, err, sizeof err);
 	if (rc) dspfft_motion_set_error(err);
 	return rc;
 }

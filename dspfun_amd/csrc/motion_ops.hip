@@ -3,6 +3,7 @@
 //   :652-668  keep the N coefficients of largest magnitude (--coeff-limit): radix select, no full sort
 //   :755-776  output scaling (scalefactor, normalization), spectrogram encodes (--spec abs / shift / flat), clamp + lround
 //   :632-633, :768-769  --linear on float pixels: the transfer characteristic's decode on load, encode on store
+//   :625,633, :769,776   --linear on 8-bit pixels: the decode is a 256-entry table, encode + clamp + lround a search in 255 thresholds (trc_u8_core.h)
 // Scalar math in double (`intermediate` of the reference's motion build, motion/Makefile:1-2).
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -11,10 +12,13 @@
 #include <math.h>
 #include <stdio.h>
 #include <algorithm>
+#include <map>
+#include <mutex>
 
 #include "../../include/dspfft.h"
 #include "motion_filter.h"
 #include "trc_core.h"
+#include "trc_u8_core.h"
 #include "topn_core.h"
 
 static_assert(dspfft::MOTION_MODE_NONE == DSPFFT_MOTION_NONE && dspfft::MOTION_MODE_ABS == DSPFFT_MOTION_ABS && dspfft::MOTION_MODE_SHIFT == DSPFFT_MOTION_SHIFT &&
@@ -75,6 +79,88 @@ __global__ void motion_linear_kernel(float *dst, const float *src, Reg r, int st
 			dst[o] = (float)(pel / 255);                                            // :774
 		}
 	}
+}
+
+// motion --linear with 8-bit pixels (trc_u8_core.h): both tables lie in LDS.  The byte of a linear value is found by comparisons with the
+// threshold table alone, from a single-precision guess (trc_u8_seed), so no pow runs here and the bytes are the host's exact evaluation's.
+// Strided 3-D regions (the block inside its embedding; the scaled region of a `scaled != block` roundtrip) ...
+struct Reg3 { int n[3]; long long sd[3], ss[3]; };
+__global__ void __launch_bounds__(256) u8_trc_region_load_kernel(float *dst, const uint8_t *src, Reg3 r, const dspfft::TrcU8Tab *tab)
+{
+	__shared__ float lut[256];
+	lut[threadIdx.x] = tab->lut[threadIdx.x];
+	__syncthreads();
+	const size_t total = (size_t)r.n[0] * r.n[1] * r.n[2];
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+		const long long x = (long long)(i % r.n[2]), y = (long long)((i / r.n[2]) % r.n[1]), z = (long long)(i / ((size_t)r.n[2] * r.n[1]));
+		dst[z * r.sd[0] + y * r.sd[1] + x * r.sd[2]] = lut[src[z * r.ss[0] + y * r.ss[1] + x * r.ss[2]]];       // :625,633,637
+	}
+}
+// pel = c * m0 * m1; pel *= m2: the reference's order with (scalefactor, normalization, normalization), a plain product with (mul, 1, 1)
+__global__ void __launch_bounds__(256) u8_trc_region_store_kernel(uint8_t *dst, const float *src, Reg3 r, double m0, double m1, double m2, int trc, const dspfft::TrcU8Tab *tab)
+{
+	TRC_NO_CONTRACT
+	__shared__ double thr[256];
+	thr[threadIdx.x] = tab->thr[threadIdx.x];
+	__syncthreads();
+	const dspfft::TrcParams tp = dspfft::trc_params(trc);
+	const size_t total = (size_t)r.n[0] * r.n[1] * r.n[2];
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+		const long long x = (long long)(i % r.n[2]), y = (long long)((i / r.n[2]) % r.n[1]), z = (long long)(i / ((size_t)r.n[2] * r.n[1]));
+		double pel = (double)src[z * r.ss[0] + y * r.ss[1] + x * r.ss[2]] * m0 * m1;                              // :759
+		pel *= m2;                                                                                                // :767
+		dst[z * r.sd[0] + y * r.sd[1] + x * r.sd[2]] = (uint8_t)dspfft::trc_u8_byte_from(thr, pel, dspfft::trc_u8_seed(tp, pel));   // :769,776
+	}
+}
+// ... and the flat pair beside dspfft_u8_to_f32 / dspfft_f32_to_u8.  vec: src is 4-byte (16-byte) and dst 16-byte (4-byte) aligned, and a
+// thread moves four samples at a time; the len % 4 samples at the end, and everything of an unaligned call, go one by one.
+__global__ void __launch_bounds__(256) u8_to_f32_trc_kernel(float *dst, const uint8_t *src, uint64_t len, int vec, const dspfft::TrcU8Tab *tab)
+{
+	__shared__ float lut[256];
+	lut[threadIdx.x] = tab->lut[threadIdx.x];
+	__syncthreads();
+	const uint64_t nq = vec ? len / 4 : 0, stride = (uint64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+	for (uint64_t q = t0; q < nq; q += stride) {
+		const uint32_t w4 = reinterpret_cast<const uint32_t *>(src)[q];
+		float4 v;
+		v.x = lut[w4 & 0xffu]; v.y = lut[(w4 >> 8) & 0xffu]; v.z = lut[(w4 >> 16) & 0xffu]; v.w = lut[w4 >> 24];
+		reinterpret_cast<float4 *>(dst)[q] = v;
+	}
+	for (uint64_t i = 4 * nq + t0; i < len; i += stride) dst[i] = lut[src[i]];
+}
+__global__ void __launch_bounds__(256) f32_to_u8_trc_kernel(uint8_t *dst, const float *src, double mul, uint64_t len, int vec, int trc, const dspfft::TrcU8Tab *tab)
+{
+	TRC_NO_CONTRACT
+	__shared__ double thr[256];
+	thr[threadIdx.x] = tab->thr[threadIdx.x];
+	__syncthreads();
+	const dspfft::TrcParams tp = dspfft::trc_params(trc);
+	auto byte = [&](float c) { const double pel = (double)c * mul; return dspfft::trc_u8_byte_from(thr, pel, dspfft::trc_u8_seed(tp, pel)); };
+	const uint64_t nq = vec ? len / 4 : 0, stride = (uint64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+	for (uint64_t q = t0; q < nq; q += stride) {
+		const float4 v = reinterpret_cast<const float4 *>(src)[q];
+		reinterpret_cast<uint32_t *>(dst)[q] = byte(v.x) | (byte(v.y) << 8) | (byte(v.z) << 16) | (byte(v.w) << 24);
+	}
+	for (uint64_t i = 4 * nq + t0; i < len; i += stride) dst[i] = (uint8_t)byte(src[i]);
+}
+
+// The tables of the calls that come without a plan: built on the host once per device and function, uploaded (synchronously) on first use
+// and kept for the life of the process (3 KB each).  A plan that has been given a function (dspfft_plan_set_u8_trc) brings its own.
+const dspfft::TrcU8Tab *cached_tab(int trc)
+{
+	static std::mutex mu;
+	static std::map<std::pair<int, int>, dspfft::TrcU8Tab *> cache;
+	int dev = 0;
+	if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+	std::lock_guard<std::mutex> lock(mu);
+	auto it = cache.find({dev, trc});
+	if (it != cache.end()) return it->second;
+	dspfft::TrcU8Tab host, *d = nullptr;
+	dspfft::trc_u8_tab_build(host, trc);
+	if (hipMalloc((void **)&d, sizeof host) != hipSuccess) return nullptr;
+	if (hipMemcpy(d, &host, sizeof host, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
+	cache[{dev, trc}] = d;
+	return d;
 }
 
 // ---- top-N by magnitude: radix select on the bits of |c| (monotone for non-negative floats) ----
@@ -179,6 +265,7 @@ size_t scan_temp(size_t n)
 
 extern "C" const char *dspfft_motion_last_error(void) { return g_merr; }
 extern "C" __attribute__((visibility("hidden"))) int dspfft_motion_set_error(const char *m) { return mbad(m); }   // (motion_dither.hip)
+extern "C" __attribute__((visibility("hidden"))) const void *dspfft_u8_trc_cached_tab(int trc) { return cached_tab(trc); }   // (motion_dither.hip, block_trc.hip)
 
 extern "C" int dspfft_motion_load_u8(float *d_coeffs, const uint8_t *d_pix, const int n[3], const int minbuf_hw[2], int ispec_mode, double ic, double normalization, void *stream)
 {
@@ -224,6 +311,33 @@ extern "C" __attribute__((visibility("hidden"))) int dspfft_motion_linear_launch
 {
 	Reg r; r.n[0] = n[0]; r.n[1] = n[1]; r.n[2] = n[2]; r.mh = minbuf_hw[0]; r.mw = minbuf_hw[1];
 	hipLaunchKernelGGL(motion_linear_kernel, dim3(mgrid((size_t)n[0] * n[1] * n[2])), dim3(256), 0, (hipStream_t)stream, d_dst, d_src, r, store, scalefactor, normalization, trc);
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+/* The 8-bit --linear launchers (engine.cpp has checked the arguments and reaches these through weak references).  tab: the device tables of
+ * a plan (dspfft_plan_set_u8_trc), or NULL for this file's own.  store = 0: dst floats = lut[src bytes]; 1: dst bytes from src floats. */
+extern "C" __attribute__((visibility("hidden"))) int dspfft_u8_trc_flat_launch(void *d_dst, const void *d_src, double mul, uint64_t len, int store, int trc, const void *tab, void *stream)
+{
+	const dspfft::TrcU8Tab *t = tab ? (const dspfft::TrcU8Tab *)tab : cached_tab(trc);
+	if (!t) return -4;
+	if (!len) return 0;
+	const uintptr_t p8 = (uintptr_t)(store ? d_dst : d_src), pf = (uintptr_t)(store ? d_src : d_dst);
+	const int vec = !(p8 & 3u) && !(pf & 15u);
+	const dim3 grid(mgrid(vec ? (len + 3) / 4 : len));
+	if (store) hipLaunchKernelGGL(f32_to_u8_trc_kernel, grid, dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_dst, (const float *)d_src, mul, len, vec, trc, t);
+	else hipLaunchKernelGGL(u8_to_f32_trc_kernel, grid, dim3(256), 0, (hipStream_t)stream, (float *)d_dst, (const uint8_t *)d_src, len, vec, t);
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+extern "C" __attribute__((visibility("hidden"))) int dspfft_u8_trc_region_launch(void *d_dst, const void *d_src, const int n[3], const long long sdst[3], const long long ssrc[3], int store,
+                                                                                  double m0, double m1, double m2, int trc, const void *tab, void *stream)
+{
+	const dspfft::TrcU8Tab *t = tab ? (const dspfft::TrcU8Tab *)tab : cached_tab(trc);
+	if (!t) return -4;
+	Reg3 r;
+	for (int k = 0; k < 3; k++) { r.n[k] = n[k]; r.sd[k] = sdst[k]; r.ss[k] = ssrc[k]; }
+	const dim3 grid(mgrid((size_t)n[0] * n[1] * n[2]));
+	if (store) hipLaunchKernelGGL(u8_trc_region_store_kernel, grid, dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_dst, (const float *)d_src, r, m0, m1, m2, trc, t);
+	else hipLaunchKernelGGL(u8_trc_region_load_kernel, grid, dim3(256), 0, (hipStream_t)stream, (float *)d_dst, (const uint8_t *)d_src, r, t);
 	return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -106,6 +106,12 @@ class Plan:
             self._check(self._lib.dspfft_plan_set_axis_scale0(self._h, axis, in_scale0, out_scale0))
         return self
 
+    def set_u8_trc(self, trc):
+        """dspfft_plan_set_u8_trc (motion --linear on 8-bit video): this plan decodes at its 8-bit load as the forward plan of a roundtrip_u8*
+        call and encodes at its 8-bit store as the inverse plan.  trc: a name or an id (trc_id); 0 / None / "none" resets."""
+        self._check(self._lib.dspfft_plan_set_u8_trc(self._h, trc_id(trc, self._lib)))
+        return self
+
     def set_input_window(self, axis, lo, hi):
         """promise that input samples of `axis` outside [lo, hi) are zero; True when the plan then skips reading (and needing) them"""
         rc = self._lib.dspfft_plan_set_input_window(self._h, axis, lo, hi)
@@ -249,10 +255,12 @@ class Plan:
 
 
 def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nblocks=(1, 1, 1), block_step=(0, 0, 0), scalefactor=1.0,
-                     normalization=1.0, stream=0, lib=None):
+                     normalization=1.0, stream=0, lib=None, trc=0):
     """dspfft_motion_dither_u8: motion.c:756-788 with -d over the {d, h, w} = n planes of every block (element (b, z, y, x) at
-    sum(b_i block_step_i) + z plane_pitch + y row_pitch + x in both buffers); d_coeffs is only read"""
+    sum(b_i block_step_i) + z plane_pitch + y row_pitch + x in both buffers); d_coeffs is only read.  trc (a name or an id; 0: none):
+    motion --linear, the bytes are the encoded ones (dspfft_motion_dither_u8_trc)"""
     lib = lib or _lib.load()
+    trc = trc_id(trc, lib)
     n = [int(v) for v in n]
     g = _lib.DitherGeom()
     g.n[:] = n
@@ -260,7 +268,11 @@ def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nbloc
     g.plane_pitch = n[1] * g.row_pitch if plane_pitch is None else int(plane_pitch)
     g.nblocks[:] = [int(v) for v in nblocks]
     g.block_step[:] = [int(v) for v in block_step]
-    if lib.dspfft_motion_dither_u8(C.c_void_p(d_pix), C.c_void_p(d_coeffs), C.byref(g), float(scalefactor), float(normalization), C.c_void_p(stream)):
+    if trc:
+        rc = lib.dspfft_motion_dither_u8_trc(C.c_void_p(d_pix), C.c_void_p(d_coeffs), C.byref(g), float(scalefactor), float(normalization), trc, C.c_void_p(stream))
+    else:
+        rc = lib.dspfft_motion_dither_u8(C.c_void_p(d_pix), C.c_void_p(d_coeffs), C.byref(g), float(scalefactor), float(normalization), C.c_void_p(stream))
+    if rc:
         raise DspfftError(lib.dspfft_motion_last_error().decode())
 
 
@@ -344,6 +356,55 @@ def motion_store_f32_linear(d_pix, d_coeffs, n, minbuf_hw=None, scalefactor=1.0,
     DspfftError (trc_id), as does a failed launch."""
     return _motion_linear("dspfft_motion_store_f32_linear", spec_mode, (0, 4), d_pix, d_coeffs, n, minbuf_hw,
                           (float(scalefactor), float(normalization)), trc, stream, lib)
+
+
+def motion_load_u8_linear(d_coeffs, d_pix, n, minbuf_hw=None, trc="iec61966-2-1", ispec_mode="none", stream=0, lib=None):
+    """dspfft_motion_load_u8_linear (motion --linear on 8-bit pixels, motion.c:625,633): coeff = lut[byte].  Returns as
+    motion_load_f32_linear does."""
+    return _motion_linear("dspfft_motion_load_u8_linear", ispec_mode, (0,), d_coeffs, d_pix, n, minbuf_hw, (), trc, stream, lib)
+
+
+def motion_store_u8_linear(d_pix, d_coeffs, n, minbuf_hw=None, scalefactor=1.0, normalization=1.0, trc="iec61966-2-1", spec_mode="none",
+                           stream=0, lib=None):
+    """dspfft_motion_store_u8_linear (motion.c:759,767-769,776): the byte of the encoded pel.  Returns as motion_store_f32_linear does."""
+    return _motion_linear("dspfft_motion_store_u8_linear", spec_mode, (0, 4), d_pix, d_coeffs, n, minbuf_hw,
+                          (float(scalefactor), float(normalization)), trc, stream, lib)
+
+
+def u8_to_f32_trc(src, trc, out=None, stream=None, lib=None):
+    """dspfft_u8_to_f32_trc over a contiguous uint8 device tensor: out = lut[src], the decode of motion --linear on 8-bit pixels (trc 0:
+    the plain conversion, dspfft_u8_to_f32).  out: a float32 tensor of the same size; a new one by default."""
+    import torch
+    lib = lib or _lib.load()
+    trc = trc_id(trc, lib)
+    if out is None:
+        out = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    assert src.is_contiguous() and out.is_contiguous() and src.numel() == out.numel() and src.element_size() == 1 and out.element_size() == 4
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    a = (C.c_void_p(out.data_ptr()), C.c_void_p(src.data_ptr()), src.numel())
+    rc = lib.dspfft_u8_to_f32_trc(*a, trc, C.c_void_p(stream)) if trc else lib.dspfft_u8_to_f32(*a, C.c_void_p(stream))
+    if rc:
+        raise DspfftError(lib.dspfft_last_error().decode())
+    return out
+
+
+def f32_to_u8_trc(src, trc, mul=1.0, out=None, stream=None, lib=None):
+    """dspfft_f32_to_u8_trc over a contiguous float32 device tensor: the byte of the encoded linear value src * mul (trc 0: the plain
+    quantiser, dspfft_f32_to_u8).  out: a uint8 tensor of the same size; a new one by default."""
+    import torch
+    lib = lib or _lib.load()
+    trc = trc_id(trc, lib)
+    if out is None:
+        out = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+    assert src.is_contiguous() and out.is_contiguous() and src.numel() == out.numel() and src.element_size() == 4 and out.element_size() == 1
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    a = (C.c_void_p(out.data_ptr()), C.c_void_p(src.data_ptr()), float(mul), src.numel())
+    rc = lib.dspfft_f32_to_u8_trc(*a, trc, C.c_void_p(stream)) if trc else lib.dspfft_f32_to_u8(*a, C.c_void_p(stream))
+    if rc:
+        raise DspfftError(lib.dspfft_last_error().decode())
+    return out
 
 
 SPEC_SCALES = {"none": 0, "linear": 1, "log": 2}

@@ -268,6 +268,24 @@ int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, const uint8_t 
 int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
                                        double scalefactor, double normalization, const dspfft_motion_filter_params *filter,
                                        unsigned long long *d_coeffs_coded, void *hip_stream);
+/* motion --linear on 8-bit video (motion/motion.c:632-633,768-769): a plan used as `fwd` of any dspfft_execute_roundtrip_u8* call decodes
+ * every byte to linear light at its 8-bit load, a plan used as `inv` encodes at its 8-bit store (the dithered store included: the byte is the
+ * encoded one, the diffused error stays the reference's c - byte / (normalization^2 scalefactor), :780).  trc: an
+ * AVColorTransferCharacteristic id (dspfft_trc_from_name); 0, the default, resets: every call is then what it was, the same kernels and bytes.
+ * On 8-bit samples the arithmetic is two tables (3 KB, built on the host with its libm when the function is set, on the device with the
+ * plan until it is destroyed): the decode of a byte is one of 256 floats -- what the reference's default build (COEFF_PRECISION=F,
+ * INTERMEDIATE_PRECISION=L) stores for it, bit for bit --, and encode + clamp + lround is a step function of the linear value, 255
+ * thresholds found by bisection over the reference's lines in double; the byte is decided by comparisons with them alone.  No pow runs
+ * on the device.  Every path of the 8-bit roundtrip takes the setting: the planar row ends and a clip in slices (kernels with the table
+ * in LDS behind the line), one 3-D block, the fused small-block kernel with and without a coefficient limit, scaled != block, the unfused
+ * sweeps (dspfft_u8_to_f32_trc / dspfft_f32_to_u8_trc below; also for row kernels compiled at plan time) and the dithered store.  The result
+ * equals dspfft_u8_to_f32_trc -> dspfft_execute_roundtrip -> dspfft_f32_to_u8_trc byte for byte.  A roundtrip on float buffers ignores it.
+ * A narrowing to know of: a row kernel compiled at plan time (DSPFFT_JIT=1, a row length without a listed kernel) has no twin with tables, so
+ * with a function set that end is converted by a sweep, and the call then has to meet the sweep's layout conditions (a dense work layout
+ * for the output, identical input and work layouts for the input): a call that runs with trc 0 through such a kernel's fused end on another
+ * layout is refused with -2 once a function is set, and a clip whose rows are such kernels is not walked in slices.
+ * -1: an f64 plan, or a trc that is not built; -3: a library without the HIP kernels (and trc != 0). */
+int dspfft_plan_set_u8_trc(dspfft_plan plan, int trc);
 
 /* The two calls above with motion's --coeff-limit (motion/motion.c:652-668) between the forward transform and the filter: of every block's
  * coefficients -- as the forward plan writes them, which with motion's per-axis index-0 factors (dspfft_plan_set_axis_scale0, :644-647) are
@@ -478,6 +496,14 @@ int dspfft_motion_store_f32(float *d_pix, const float *d_coeffs, const int n[3],
 int dspfft_motion_load_f32_linear(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], int trc, void *hip_stream);
 int dspfft_motion_store_f32_linear(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2],
                                    double scalefactor, double normalization, int trc, void *hip_stream);
+/* the 8-bit pair with motion --linear (--ispec / --spec none; a copy store alike), through the two tables of dspfft_plan_set_u8_trc:
+ * load  coeff = lut[byte] = (float)(decode(byte / 255) * 255) as the reference's default (long double) build stores it      (motion.c:625,633,637)
+ * store pel = coeff * scalefactor * normalization; pel *= normalization (double); byte = clamp(lround(encode(pel / 255) * 255))   (:759,767-769,776)
+ * -1 for a trc that is 0 or not built.  The tables of these calls (and of the flat pair and the dithered store below) are uploaded once per
+ * device and function, synchronously at the first call that needs them, and kept for the life of the process. */
+int dspfft_motion_load_u8_linear(float *d_coeffs, const uint8_t *d_pix, const int n[3], const int minbuf_hw[2], int trc, void *hip_stream);
+int dspfft_motion_store_u8_linear(uint8_t *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2],
+                                  double scalefactor, double normalization, int trc, void *hip_stream);
 /* motion.c:756-788 with -d / --dither (spec none, 8-bit pixels, !linear): the 8-bit store with 2-D Floyd-Steinberg error diffusion, plane
  * by plane (the z planes of a block are independent, and so are blocks).  Per pixel, in raster order: pel = c * scalefactor * normalization,
  * pel *= normalization, byte = clamp + lround, dp = c - byte / (normalization^2 scalefactor), and dp * 7/16, 3/16, 5/16, 1/16 go into the
@@ -499,6 +525,11 @@ typedef struct {
 	long long block_step[3];                /* elements between neighbouring blocks along each of them */
 } dspfft_dither_geom;
 int dspfft_motion_dither_u8(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor, double normalization, void *hip_stream);
+/* the same with motion --linear: the byte is clamp(lround(encode(pel / 255) * 255)) (:769,776), found in the threshold table of
+ * dspfft_plan_set_u8_trc; the error is still c - byte / (normalization^2 scalefactor) (:780: the reference subtracts an encoded byte from a
+ * linear coefficient, and so does this).  Byte-identical to the reference's lines built F / D with linear = true.  -1 for a trc that is 0 or
+ * not built. */
+int dspfft_motion_dither_u8_trc(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor, double normalization, int trc, void *hip_stream);
 /* motion.c:652-668 (--coeff-limit): keep the `keep` coefficients of largest magnitude among d_coeffs[0 .. count), zero the rest.
  * Radix select on the device (four histogram passes over the bits of |c|, no sort).  Ties at the threshold: the reference's choice
  * depends on qsort; here the earliest in buffer order are kept -- documented, deterministic. */
@@ -526,6 +557,12 @@ int dspfft_u8_to_f32(float *d_dst, const uint8_t *d_src, uint64_t len, void *hip
 
 /* motion/motion.c:756-776 (spec none, !linear, 8-bit output): pix = clamp(lround(c * mul), 0, 255). */
 int dspfft_f32_to_u8(uint8_t *d_dst, const float *d_src, double mul, uint64_t len, void *hip_stream);
+
+/* the same two with motion --linear (motion.c:633, :769): dst = lut[src], and dst = the byte of the linear value (double)src * mul, by the
+ * tables of dspfft_plan_set_u8_trc.  Any alignment; 4-byte aligned bytes beside 16-byte aligned floats move four samples per lane.
+ * -1 for a trc that is 0 or not built. */
+int dspfft_u8_to_f32_trc(float *d_dst, const uint8_t *d_src, uint64_t len, int trc, void *hip_stream);
+int dspfft_f32_to_u8_trc(uint8_t *d_dst, const float *d_src, double mul, uint64_t len, int trc, void *hip_stream);
 
 /* ---- zoom's dense basis product on the f32 matrix cores ---- */
 

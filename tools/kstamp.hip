@@ -4,7 +4,7 @@
 // unstamped) -- read the phase SHARES, never compare a stamped kernel's total with an unstamped one's.
 //
 //   hipcc -std=c++17 -O3 -fno-slp-vectorize -ffp-contract=on --offload-arch=gfx950 -Idspfun_amd/csrc -Iinclude tools/kstamp.hip -o tools/kstamp
-//   tools/kstamp [pair|half|rt|zoomx|u8]
+//   tools/kstamp [pair|half|rt|zoomx|u8|trc]
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -15,6 +15,7 @@
 __device__ unsigned long long *g_stamps;
 #define DSP_STAMP(i) do { if (g_stamps && threadIdx.x == 0) g_stamps[(size_t)blockIdx.x * 32 + (i)] = clock64(); } while (0)
 #include "spec_kernels.h"
+#include "spec_row_trc.h"
 
 using namespace dspfft;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(1); } } while (0)
@@ -90,7 +91,7 @@ template <class S> static void rt_case(float *x, const char *what)
 int main(int argc, char **argv)
 {
 	setvbuf(stdout, NULL, _IONBF, 0);
-	const char *which = argc > 1 ? argv[1] : "pair half rt zoomx u8";
+	const char *which = argc > 1 ? argv[1] : "pair half rt zoomx u8 trc";
 	const int W8 = 7680, H8 = 4320;
 	const size_t n8 = (size_t)W8 * H8 * 3;
 	float *x;
@@ -157,6 +158,43 @@ int main(int argc, char **argv)
 		run("row_spec_u8 1920 REDFT10 (u8 -> f32, 276480 lines)", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_kernel<S, 0>), dim3(lines), dim3(S::T), S::LDS, 0, a, io); });
 		a.kind = 1; io.in = nullptr; io.out = p8; io.mul = 1.0 / 3840.0;
 		run("row_spec_u8 1920 REDFT01 (f32 -> u8)", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_kernel<S, 1>), dim3(lines), dim3(S::T), S::LDS, 0, a, io); });
+	}
+	if (strstr(which, "trc")) {
+		// the same rows with motion --linear (dspfft_plan_set_u8_trc, iec61966-2-1) beside the plain 8-bit ends: the tables in LDS behind the plane, or left
+		// in global memory for the vector L1 (spec_row_trc.h TLDS).  Random bytes / floats spread over the byte range: the table reads scatter as a clip's do.
+		typedef RowSpec<1920, 1, 128, 8, 8, 15> S;
+		const int w = 1920, lines = 1080 * 256;
+		uint8_t *p8; float *pf32;
+		CK(hipMalloc(&p8, (size_t)w * lines)); CK(hipMalloc(&pf32, (size_t)w * lines * 4));
+		{
+			std::vector<uint8_t> hb((size_t)w * 1080);
+			unsigned s = 777;
+			for (size_t i = 0; i < hb.size(); i++) { s = s * 1664525u + 1013904223u; hb[i] = (uint8_t)(s >> 24); }
+			for (int i = 0; i < 256; i++) CK(hipMemcpy(p8 + (size_t)i * w * 1080, hb.data(), hb.size(), hipMemcpyHostToDevice));
+		}
+		for (int i = 0; i < 256; i += 32) CK(hipMemcpy(pf32 + (size_t)i * w * 1080, x, (size_t)w * 1080 * 32 * 4, hipMemcpyDeviceToDevice));
+		TrcU8Tab host, *tab;
+		trc_u8_tab_build(host, TRC_IEC61966_2_1);
+		CK(hipMalloc(&tab, sizeof host)); CK(hipMemcpy(tab, &host, sizeof host, hipMemcpyHostToDevice));
+		PassArgs a = {};
+		a.N = S::N; a.C = 1; a.nb0 = lines; a.nb1 = 1; a.sb0_in = a.sb0_out = w; a.nlines = lines;
+		a.in = pf32; a.out = pf32; a.T = tab_T(S::N); a.W = tab_W(S::L); a.scale = 1.f; a.in_scale0 = a.out_scale0 = 1.f;
+		U8IOTrc io = {};
+		io.tab_in = io.tab_out = tab; io.trc_out = TRC_IEC61966_2_1;
+		const size_t l10 = S::LDS + trc_lds_bytes<0>(), l01 = S::LDS + trc_lds_bytes<1>();
+		for (int rep = 0; rep < 2; rep++) {         // (twice: the spread between the two rounds is the noise to read the differences against)
+			a.kind = 0; io.in = p8; io.out = nullptr; io.mul = 1.0;
+			run("row_spec_u8     1920 REDFT10 plain", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_kernel<S, 0>), dim3(lines), dim3(S::T), S::LDS, 0, a, io); });
+			run("row_spec_u8_trc 1920 REDFT10 tables in LDS", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_trc_kernel<S, 0, true>), dim3(lines), dim3(S::T), l10, 0, a, io); });
+			run("row_spec_u8_trc 1920 REDFT10 tables in global memory", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_trc_kernel<S, 0, false>), dim3(lines), dim3(S::T), S::LDS, 0, a, io); });
+			// the inverse's output spread over 0..255 in linear light: x in [0, 1), scale 255 / (row gain) is not needed for time -- any spread of bytes will do
+			a.kind = 1; io.in = nullptr; io.out = p8; io.mul = 1.0 / 15.0;
+			for (int i = 0; i < 256; i += 32) CK(hipMemcpy(pf32 + (size_t)i * w * 1080, x, (size_t)w * 1080 * 32 * 4, hipMemcpyDeviceToDevice));
+			run("row_spec_u8     1920 REDFT01 plain", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_kernel<S, 1>), dim3(lines), dim3(S::T), S::LDS, 0, a, io); });
+			run("row_spec_u8_trc 1920 REDFT01 tables in LDS", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_trc_kernel<S, 1, true>), dim3(lines), dim3(S::T), l01, 0, a, io); });
+			run("row_spec_u8_trc 1920 REDFT01 tables in global memory", lines, [&]() { hipLaunchKernelGGL((row_spec_u8_trc_kernel<S, 1, false>), dim3(lines), dim3(S::T), S::LDS, 0, a, io); });
+			for (int i = 0; i < 256; i += 32) CK(hipMemcpy(pf32 + (size_t)i * w * 1080, x, (size_t)w * 1080 * 32 * 4, hipMemcpyDeviceToDevice));
+		}
 	}
 	if (strstr(which, "zoomx")) {
 		// zoom's x stage of BASELINE config 3: 2160 lines of 1920 pixels (3 floats) -> 7680 pixels; the table's values do not matter for time
