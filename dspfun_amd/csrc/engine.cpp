@@ -29,6 +29,7 @@
 #include "trc_core.h"
 #include "topn_core.h"
 #include "block_rt.h"
+#include "block_rs_core.h"
 #include "trc_u8_core.h"
 
 using namespace dspfft;
@@ -62,6 +63,8 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_u8_trc_region_
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_trc_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor,
                                                                                      double normalization, int trc, const void *tab, void *stream, char *err, size_t errlen);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_trc_launch(const dspfft::BlockRtTrcArgs *a, int nwg, size_t lds, void *stream);
+// block_rescale.hip's launcher behind a roundtrip over a rescaled block grid (motion -b with -s).  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_launch(const dspfft::BlockRsArgs *a, int nwg, size_t lds, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_row_u8_trc_launch(int row_spec_id, const dspfft::PassArgs *a, const dspfft::U8IOTrc *io, int nwg, void *stream);
 
 static thread_local char g_err[512] = "";
@@ -1794,6 +1797,9 @@ struct RtCall {
 	TopnRuns runs;                        // keep != 0 and not `block`: the blocks as contiguous runs of the working buffer
 	U8Trc trc_in, trc_out;                // dspfft_plan_set_u8_trc of the forward plan (8-bit input) and of the inverse plan (8-bit or dithered output)
 	bool dithered;                        // set by roundtrip_core before rt_check: the bytes come from the dither kernel
+	bool grid;                            // a rescaled block grid (rt_grid): block_rescale.hip's kernel runs the call, out of place
+	BlockRsArgs rs;                       // its geometry, derived for the pair
+	int rs_nwg; size_t rs_lds;
 };
 // the conversions at the ends of the unfused paths, plain or through the call's transfer characteristic
 int rt_u8_in(const RtCall &c, float *dst, uint64_t len)
@@ -1805,13 +1811,90 @@ int rt_u8_out(const RtCall &c, const float *src, uint64_t len)
 	return c.trc_out.id ? dspfft_u8_trc_flat_launch(c.d_out8, src, c.mul8, len, 1, c.trc_out.id, c.trc_out.tab, c.stream) : be_f32_to_u8(c.d_out8, src, c.mul8, len, c.stream);
 }
 
+// motion -b with -s over a block grid (motion.c:488-499,535-552): both plans cut their volumes into small blocks, `fwd` the input volume
+// into blocks of `block`, `inv` the output volume into as many blocks of `scaled`.  0: the pair is none (the call goes on as before: every
+// such pair was refused until now); 1: it is one, c.grid and c.rs are set and everything about the call is checked; < 0: it is almost one,
+// or the call cannot run.  Nothing is launched here.
+int rt_grid(RtCall &c)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	bool differs = fwd->rank != inv->rank;
+	for (int a = 0; !differs && a < fwd->rank; a++) differs = fwd->n[a] != inv->n[a];
+	if (!differs || fwd->howmany < 2 || inv->howmany < 2) return 0;
+	const char *const what = "roundtrip with different forward / inverse extents over a grid of blocks";
+	if (fwd->rank != inv->rank) return fail(-2, "%s: the plans have different ranks (%d-D blocks against %d-D blocks)", what, fwd->rank, inv->rank);
+	if (!fwd->has_block || !inv->has_block)
+		return fail(-2, "%s: every extent of both plans must be 4, 8 or 16 (2-D blocks: 32 too), x contiguous, all strides multiples of 4 (a single block goes with howmany = 1)", what);
+	if (fwd->blk_kind != KIND_REDFT10 || inv->blk_kind != KIND_REDFT01) return fail(-2, "%s: the forward plan must be REDFT10 and the inverse REDFT01 on every axis", what);
+	const BlockGeom &f = fwd->blk, &i = inv->blk;
+	for (int k = 0; k < 3; k++) if (fwd->blk_axis[k] != inv->blk_axis[k]) return fail(-2, "%s: the plans order their axes differently", what);
+	if (f.rows_fast != i.rows_fast) return fail(-2, "%s: one plan is a block-major stack and the other the blocks of a volume", what);
+	bool same = f.nxb == i.nxb && f.nd == i.nd;
+	for (int d = 0; same && d < f.nd; d++) same = f.bn[d] == i.bn[d];
+	if (!same || fwd->howmany != inv->howmany) return fail(-2, "%s: the plans count different numbers of blocks", what);
+	if (!dspfft_block_rescale_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale.hip)", what);
+	BlockRsArgs &r = c.rs;
+	memset(&r, 0, sizeof r);
+	static_cast<BlockGeom &>(r) = f;
+	r.sy_out = i.sy_out; r.sz_out = i.sz_out; r.sxb_out = i.sxb_out;
+	for (int d = 0; d < i.nd; d++) r.bos[d] = i.bos[d];
+	r.ox = i.nx; r.oy = i.ny; r.oz = i.nz;
+	const int mx = std::max(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
+	if (c.keep && c.keep < (size_t)mx * my * mz)
+		return fail(-2, "%s: a coefficient limit is not implemented here (the reference selects over the whole embedding, motion.c:652-668)", what);
+	c.keep = 0;
+	const uintptr_t pin = c.d_in8 ? (uintptr_t)c.d_in8 : (uintptr_t)c.d_in, pout = c.d_out8 ? (uintptr_t)c.d_out8 : (uintptr_t)c.d_out;
+	if (((c.d_in8 ? 3u : 15u) & pin) || ((c.d_out8 ? 3u : 15u) & pout)) return fail(-2, "%s: float buffers must be 16-byte aligned, 8-bit buffers 4-byte aligned", what);
+	memset(&c.mf, 0, sizeof c.mf);
+	if (c.fp) {
+		if (c.fp->preserve_dc < 0 || c.fp->preserve_dc > 2 || c.fp->minbuf_hw[0] < 1 || c.fp->minbuf_hw[1] < 1 || c.fp->block_depth < 1) return fail(-1, "bad filter parameters");
+		motion_filter_of(*c.fp, c.mf);
+	}
+	if (c.d_in8 && fwd->u8_trc) c.trc_in = U8Trc{fwd->u8_trc, fwd->u8_tab};
+	if ((c.d_out8 || c.dithered) && inv->u8_trc) c.trc_out = U8Trc{inv->u8_trc, inv->u8_tab};
+	// blocks per workgroup: build_block's rule on the embedding with tiles of twice the size -- about 8192 samples (32 KB), rows of at most
+	// 1 KB.  The pruned phases have min(block, scaled) columns per block, so build_block's 4096 samples leave half the workgroup idle in them
+	// (1920x1080x64, 8-bit: 8x8x8 -> 4x4x4 1.17 -> 1.43 TB/s, 16x16x16 -> 8x8x8 0.92 -> 1.29, profiles/r09_motion_block_rescale.txt).  The
+	// tables and the counter fit behind such a tile; a forced G gives way until they do.
+	int G;
+	{
+		EnvScope env(fwd->plan_env);
+		G = env_int("DSPFFT_BLOCK_G");
+	}
+	if (G < 1) G = std::min(256 / mx, 8192 / (mx * my * mz));
+	G = std::max(1, std::min(G, f.nxb));
+	while (G > 1 && (size_t)mz * my * G * mx * sizeof(float) + sizeof(TrcU8Tab) + 16 > 64 * 1024) G--;
+	r.tw = mx; r.G = G; r.pitch = G * mx; r.ngroups = (f.nxb + G - 1) / G; r.gdiv = make_div((uint32_t)r.ngroups);
+	long long nwg = r.ngroups;
+	for (int d = 0; d < r.nd; d++) nwg *= r.bn[d];
+	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch", what);
+	c.rs_nwg = (int)nwg; c.rs_lds = (size_t)mz * my * r.pitch * sizeof(float);
+	c.grid = true;
+	return 1;
+}
+
+// a rescaled block grid: load, forward over `block`, filter, inverse over `scaled`, store -- one launch, from the forward plan's input layout
+// into the inverse plan's output layout
+int rt_run_grid(const RtCall &c)
+{
+	BlockRsArgs a = c.rs;
+	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
+	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
+	a.filt = c.mf; a.coded = c.coded;
+	a.tab_in = (const TrcU8Tab *)c.trc_in.tab; a.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; a.trc_out = c.trc_out.id;
+	if (int rc = dspfft_block_rescale_launch(&a, c.rs_nwg, c.rs_lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid): backend code %d", rc);
+	return 0;
+}
+
 // every rejection of a roundtrip call; nothing has been launched when it returns
 int rt_check(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
 	const dspfft_motion_filter_params *fp = c.fp;
-	if (!fwd || !inv || !(c.d_in || c.d_in8) || !c.d_out) return fail(-1, "null plan or buffer");
+	if (!fwd || !inv || !(c.d_in || c.d_in8) || !(c.d_out || c.d_out8)) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
+	if (int g = rt_grid(c)) return g < 0 ? g : 0;
+	if (!c.d_out) return fail(-1, "null plan or buffer");       // (only a rescaled block grid stores its bytes without a float work buffer)
 	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
 	const Pass &F = *(c.F = &fwd->passes[nf - 1]), &I = *(c.I = &inv->passes[0]);
 	bool differs = fwd->rank != inv->rank;
@@ -2166,7 +2249,8 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 	c.dithered = dither != nullptr;
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
-	if (c.block) rc = rt_run_block(c);
+	if (c.grid) rc = rt_run_grid(c);
+	else if (c.block) rc = rt_run_block(c);
 	else if (c.rescale) rc = rt_run_rescale(c);
 	else {
 		if (may_slice && !c.keep && d_in8 && (d_out8 || dither) && c.u8_first && c.u8_last && c.F->axis == c.I->axis && (15u & (uintptr_t)d_out) == 0 && !fused_roundtrip_off())
@@ -2189,7 +2273,7 @@ extern "C" int dspfft_execute_roundtrip(dspfft_plan fwd, dspfft_plan inv, const 
 extern "C" int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
                                            const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream)
 {
-	if (!d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
+	if (!d_in || !d_out) return fail(-1, "null plan or buffer");         // (d_work: rt_check; a rescaled block grid needs none)
 	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream);
 }
 
@@ -2211,7 +2295,7 @@ extern "C" int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv
                                                 const dspfft_motion_filter_params *fp, size_t keep, void *d_topn_work, size_t work_bytes,
                                                 unsigned long long *d_coeffs_coded, void *stream)
 {
-	if (!d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
+	if (!d_in || !d_out) return fail(-1, "null plan or buffer");
 	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream, true, nullptr, keep, d_topn_work, work_bytes);
 }
 

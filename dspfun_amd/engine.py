@@ -210,7 +210,8 @@ class Plan:
     def roundtrip_u8(self, inv, d_in_u8, d_out_u8, d_work, out_mul, filter=None, d_coded=0, stream=0, coeff_limit=0, topn_work=None):
         """the same with motion's 8-bit samples at both ends (motion.c:617-640, :760-776): u8 in, float work buffer, u8 out =
         quantise(value * out_mul); the conversions ride on the first and last row passes when those are planar specialised passes.
-        coeff_limit, topn_work: as roundtrip's (dspfft_execute_roundtrip_u8_topn)."""
+        coeff_limit, topn_work: as roundtrip's (dspfft_execute_roundtrip_u8_topn).  d_work may be None / 0 for a rescaled block grid
+        (motion_grid_plans: one kernel from the input volume to the output volume, no float intermediate); every other pair needs it."""
         fp = self._filter_params(filter)
         fpp = C.byref(fp) if fp is not None else None
         if not coeff_limit:
@@ -252,6 +253,48 @@ class Plan:
     def _check(self, rc):
         if rc:
             raise DspfftError(self._lib.dspfft_last_error().decode())
+
+
+def motion_grid_plans(shape_dhw, block, scaled, lib=None):
+    """motion --blocksize `block` --size `scaled` over a [D][H][W] volume (motion/motion.c:488-499,535-552,566-567): the plan pair of
+    dspfft_execute_roundtrip* for the volume layout.  block, scaled: (d, h, w), every extent 4, 8 or 16, or d = 1 on both sides for 2-D blocks
+    of up to 32 x 32.  fwd cuts the input volume (its pitches are shape_dhw's; W a multiple of 4) into whole blocks -- what is left over at
+    the far ends is cropped, as the reference crops -- and inv cuts the dense output volume info["out_shape"] into as many blocks of
+    `scaled`.  Both carry motion's scales (2 sqrt 2 and its inverse, the per-axis index-0 factors of the uniform range, :644-647,748-751;
+    for 2-D blocks the unit axis of the reference's 3-D plans is folded into them).  info: in_shape (the cropped input extents), out_shape,
+    nblocks, active = min(block, scaled) for the filter, scalefactor, normalization, out_mul = scalefactor normalization^2 (roundtrip_u8's)."""
+    import math
+    D, H, W = (int(v) for v in shape_dhw)
+    (bd, bh, bw), (sd, sh, sw) = (tuple(int(v) for v in t) for t in (block, scaled))
+    if (bd == 1) != (sd == 1):
+        raise ValueError("block and scaled must both be 2-D (depth 1) or both 3-D")
+    if W % 4:
+        raise ValueError("the row pitch W must be a multiple of 4")
+    nd, nh, nw = D // bd, H // bh, W // bw
+    if not (nd and nh and nw):
+        raise ValueError("the volume holds no whole block")
+    Do, Ho, Wo = nd * sd, nh * sh, nw * sw
+    two_d = bd == 1
+    r2 = math.sqrt(2.0)
+
+    def plan(ext, vol, kind, scale):
+        (ed, eh, ew), (_, vh, vw) = ext, vol
+        dims = [(ed, vh * vw, vh * vw), (eh, vw, vw), (ew, 1, 1)][1 if two_d else 0:]
+        how = [(nd, ed * vh * vw, ed * vh * vw), (nh, eh * vw, eh * vw), (nw, ew, ew)]
+        return Plan.guru(dims, how, [kind] * len(dims), lib=lib).set_scale(scale)
+    # (a unit axis of the reference's 3-D plans: REDFT10 doubles and the uniform range divides by sqrt 2; the inverse multiplies by sqrt 2)
+    unit = r2 if two_d else 1.0
+    fwd = plan((bd, bh, bw), (D, H, W), REDFT10, 2 * r2 * unit)
+    inv = plan((sd, sh, sw), (Do, Ho, Wo), REDFT01, unit / (2 * r2))
+    for a in range(2 if two_d else 3):
+        fwd.set_axis_scale0(a, 1.0, 1.0 / r2)
+        inv.set_axis_scale0(a, r2, 1.0)
+    ns, nbk = float(sd * sh * sw), float(bd * bh * bw)
+    scalefactor, normalization = ns / nbk, 1.0 / math.sqrt(ns * 8)
+    info = dict(in_shape=(nd * bd, nh * bh, nw * bw), out_shape=(Do, Ho, Wo), nblocks=(nd, nh, nw),
+                active=(min(bd, sd), min(bh, sh), min(bw, sw)), scalefactor=scalefactor, normalization=normalization,
+                out_mul=scalefactor * normalization * normalization)
+    return fwd, inv, info
 
 
 def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nblocks=(1, 1, 1), block_step=(0, 0, 0), scalefactor=1.0,

@@ -242,7 +242,32 @@ int dspfft_execute_roundtrip(dspfft_plan fwd, dspfft_plan inv, const float *d_in
 /* `scaled != block` (motion/motion.c:535-552,566,644-647,748-759): `inv` may be planned over DIFFERENT extents than `fwd` inside the
  * same embedding (same strides; howmany = 1).  Larger extents zero-pad the spectrum (band-limited upscale), smaller ones truncate
  * it (downscale); the filter's `active` is min(block, scaled) per axis.  The transforms then run unfused.  The work buffer is
- * zeroed first (motion.c:619) except in place on a float buffer, where the caller has zeroed everything outside the block. */
+ * zeroed first (motion.c:619) except in place on a float buffer, where the caller has zeroed everything outside the block.
+ *
+ * A whole GRID of such blocks (motion --blocksize 8x8x8 --size 4x4x4 over a clip, motion.c:488-499,613-800) is ONE launch of this call
+ * and of its _u8, _u8_dither and _topn forms: every block is loaded, transformed over `block`, filtered over min(block, scaled),
+ * transformed back over `scaled` and stored by one kernel (block_rescale.hip), the block's embedding never leaving the chip.  The pair is
+ * such a grid when both plans are f32 small-block plans as described above (every extent of `block` and of `scaled` 4, 8 or 16, 2-D
+ * blocks up to 32; x contiguous; strides multiples of 4), `fwd` REDFT10 and `inv` REDFT01 on every axis, of the same rank and axis order,
+ * with the same numbers of blocks, and the extents differ.  Two layouts:
+ *   volume layout      both dspfft_plan_guru_r2r, each in place on its OWN volume: `fwd` over the input [D][H][W] with dims `block` and
+ *                      howmany {D/bd, H/bh, W/bw}; `inv` over the output [D sd/bd][H sh/bh][W sw/bw] with dims `scaled` and the same
+ *                      howmany counts (strides of that volume)
+ *   block-major layout both dspfft_plan_many_r2r with howmany = the number of blocks and idist = odist = the block's own volume
+ *                      (bd bh bw for `fwd`, sd sh sw for `inv`)
+ * d_in is read in `fwd`'s INPUT layout and d_out written in `inv`'s OUTPUT layout: the call is out of place by nature and the in-place
+ * layout rules above do not apply to it.  Float buffers must be 16-byte aligned, 8-bit ones 4-byte.  The filter's `active` is the caller's
+ * min(block, scaled); positions are the block's own coordinates (minbuf_hw and block_depth are not consulted).
+ *   _u8         d_work is not touched and may be NULL (for every other pair it is required)
+ *   _u8_dither  the kernel stores float into d_work in `inv`'s output layout (required here), and the dithered store writes the bytes over
+ *               the output volume block by block -- the composition the block == scaled path uses
+ *   dspfft_plan_set_u8_trc is honoured at both 8-bit ends, the dithered store included
+ *   _topn       a keep in range is refused (-2, nothing launched): the reference selects over the whole embedding, forward coefficients
+ *               outside min(block, scaled) included (motion.c:652-668), which needs a selection stage of its own -- a follow-up;
+ *               keep == 0 or keep >= the embedding's count max(block, scaled) is the plain call
+ * -2, with the reason and nothing launched, also for misaligned buffers and for a pair that is almost a grid (different block counts, 2-D
+ * against 3-D blocks, an extent outside the list); -3 from a library built without the HIP kernel.  A pair with block == scaled is the
+ * path described above: the same kernels, the same bytes. */
 
 /* The same with motion's 8-bit samples at both ends (motion/motion.c:617-640 load, :760-776 store): d_in and d_out
  * hold uint8 samples in the plans' input / output element layout, d_work is a float buffer in the plans' working
@@ -277,7 +302,8 @@ int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const u
  * INTERMEDIATE_PRECISION=L) stores for it, bit for bit --, and encode + clamp + lround is a step function of the linear value, 255
  * thresholds found by bisection over the reference's lines in double; the byte is decided by comparisons with them alone.  No pow runs
  * on the device.  Every path of the 8-bit roundtrip takes the setting: the planar row ends and a clip in slices (kernels with the table
- * in LDS behind the line), one 3-D block, the fused small-block kernel with and without a coefficient limit, scaled != block, the unfused
+ * in LDS behind the line), one 3-D block, the fused small-block kernel with and without a coefficient limit, scaled != block (one block, and
+ * a grid of blocks in its one kernel), the unfused
  * sweeps (dspfft_u8_to_f32_trc / dspfft_f32_to_u8_trc below; also for row kernels compiled at plan time) and the dithered store.  The result
  * equals dspfft_u8_to_f32_trc -> dspfft_execute_roundtrip -> dspfft_f32_to_u8_trc byte for byte.  A roundtrip on float buffers ignores it.
  * A narrowing to know of: a row kernel compiled at plan time (DSPFFT_JIT=1, a row length without a listed kernel) has no twin with tables, so
