@@ -88,6 +88,53 @@ DSP_HD void block_line_of(const BlockGeom &a, int l, int rows, int cnt, int &row
 // the tile); lut / thr NULL: that end converts plainly
 struct BlockTrc { const float *lut; const double *thr; TrcParams tp; };
 
+// ---- the two ends of a line: N samples at a global offset (every fused block kernel's load and store; the callers address the tile) ----
+// float4 loads (16-byte aligned: the planner and the engine only fuse such layouts), packed bytes, or (TRC) packed bytes through the decode
+// table `lut`, which is then not NULL
+template <int N, bool U8, bool TRC>
+DSP_HD void block_line_read(const float *in, const uint8_t *in8, long long off, const float *lut, float (&x)[N])
+{
+	if constexpr (U8) {
+#pragma unroll
+		for (int j = 0; j < N / 4; j++) {
+			uint32_t w4;
+			__builtin_memcpy(&w4, in8 + off + 4 * j, 4);
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				if constexpr (TRC) x[4 * j + q] = lut[(w4 >> (8 * q)) & 0xffu];
+				else x[4 * j + q] = (float)((w4 >> (8 * q)) & 0xffu);
+			}
+		}
+	} else {
+#pragma unroll
+		for (int j = 0; j < N / 4; j++) {
+			const float4 v = reinterpret_cast<const float4 *>(in + off)[j];
+			x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
+		}
+	}
+}
+// float4 stores, quantised bytes (motion.c:760-776), or (TRC) the encoded bytes (:769) found in the threshold table `thr`, which is then not
+// NULL; tp seeds that search
+template <int N, bool U8, bool TRC>
+DSP_HD void block_line_write(const float (&o)[N], float *out, uint8_t *out8, long long off, double mul8, const double *thr, const TrcParams &tp)
+{
+	if constexpr (U8) {
+#pragma unroll
+		for (int j = 0; j < N / 4; j++) {
+			uint32_t w4 = 0;
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				if constexpr (TRC) { const double pel = (double)o[4 * j + k] * mul8; w4 |= trc_u8_byte_from(thr, pel, trc_u8_seed(tp, pel)) << (8 * k); }
+				else w4 |= quantise_u8_of(o[4 * j + k], mul8, (float)mul8) << (8 * k);
+			}
+			__builtin_memcpy(out8 + off + 4 * j, &w4, 4);
+		}
+	} else {
+#pragma unroll
+		for (int j = 0; j < N / 4; j++) { float4 v; v.x = o[4 * j]; v.y = o[4 * j + 1]; v.z = o[4 * j + 2]; v.w = o[4 * j + 3]; reinterpret_cast<float4 *>(out + off)[j] = v; }
+	}
+}
+
 // phase x, forward side: load (float or 8-bit; TRC: 8-bit through the decode table) + x transform into the tile
 template <int NX, int NY, int NZ, int KIND, bool U8, bool TRC = false>
 DSP_HD void block_load_x(const BlockGeom &a, const TinyArgs &tx, const float *in, const uint8_t *in8, float *lds, long long bin, int cnt, int tid, const BlockTrc *t = nullptr)
@@ -99,31 +146,15 @@ DSP_HD void block_load_x(const BlockGeom &a, const TinyArgs &tx, const float *in
 		const int z = row / NY, y = row - z * NY;
 		const long long off = bin + (long long)g * a.sxb_in + (long long)z * a.sz_in + (long long)y * a.sy_in;
 		float x[NX], o[NX];
-		if constexpr (U8) {
-#pragma unroll
-			for (int j = 0; j < NX / 4; j++) {
-				uint32_t w4;
-				__builtin_memcpy(&w4, in8 + off + 4 * j, 4);
-#pragma unroll
-				for (int q = 0; q < 4; q++) {
-					if constexpr (TRC) x[4 * j + q] = t->lut ? t->lut[(w4 >> (8 * q)) & 0xffu] : (float)((w4 >> (8 * q)) & 0xffu);
-					else x[4 * j + q] = (float)((w4 >> (8 * q)) & 0xffu);
-				}
-			}
-		} else {
-#pragma unroll
-			for (int j = 0; j < NX / 4; j++) {      // 16-byte aligned: the planner only fuses such layouts
-				const float4 v = reinterpret_cast<const float4 *>(in + off)[j];
-				x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
-			}
-		}
+		if (TRC && t->lut) block_line_read<NX, U8, TRC>(in, in8, off, t->lut, x);
+		else block_line_read<NX, U8, false>(in, in8, off, nullptr, x);
 		tiny_dct<NX, KIND>(tx, x, o);
 		float4 *q = reinterpret_cast<float4 *>(lds + row * a.pitch + g * NX);
 #pragma unroll
 		for (int j = 0; j < NX / 4; j++) { float4 v; v.x = o[4 * j]; v.y = o[4 * j + 1]; v.z = o[4 * j + 2]; v.w = o[4 * j + 3]; q[j] = v; }
 	}
 }
-// phase x, inverse side: x transform out of the tile + store (float or quantised 8-bit, motion.c:760-776; TRC: the encoded byte, :769)
+// phase x, inverse side: x transform out of the tile + store (float or quantised 8-bit; TRC: the encoded byte)
 template <int NX, int NY, int NZ, int KIND, bool U8, bool TRC = false>
 DSP_HD void block_store_x(const BlockGeom &a, const TinyArgs &tx, float *out, uint8_t *out8, double mul8, const float *lds, long long bout, int cnt, int tid, const BlockTrc *t = nullptr)
 {
@@ -138,23 +169,8 @@ DSP_HD void block_store_x(const BlockGeom &a, const TinyArgs &tx, float *out, ui
 #pragma unroll
 		for (int j = 0; j < NX / 4; j++) { const float4 v = q[j]; x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w; }
 		tiny_dct<NX, KIND>(tx, x, o);
-		if constexpr (U8) {
-#pragma unroll
-			for (int j = 0; j < NX / 4; j++) {
-				uint32_t w4 = 0;
-#pragma unroll
-				for (int k = 0; k < 4; k++) {
-					if constexpr (TRC) {
-						if (t->thr) { const double pel = (double)o[4 * j + k] * mul8; w4 |= trc_u8_byte_from(t->thr, pel, trc_u8_seed(t->tp, pel)) << (8 * k); continue; }
-					}
-					w4 |= quantise_u8_of(o[4 * j + k], mul8, (float)mul8) << (8 * k);
-				}
-				__builtin_memcpy(out8 + off + 4 * j, &w4, 4);
-			}
-		} else {
-#pragma unroll
-			for (int j = 0; j < NX / 4; j++) { float4 v; v.x = o[4 * j]; v.y = o[4 * j + 1]; v.z = o[4 * j + 2]; v.w = o[4 * j + 3]; reinterpret_cast<float4 *>(out + off)[j] = v; }
-		}
+		if (TRC && t->thr) block_line_write<NX, U8, TRC>(o, out, out8, off, mul8, t->thr, t->tp);
+		else block_line_write<NX, U8, false>(o, out, out8, off, mul8, nullptr, TrcParams());
 	}
 }
 // phases y / z: lines of N samples `stride` floats apart in the tile

@@ -1,7 +1,8 @@
-// block_fused.hip -- kernels of the fused small-block passes (block_core.h) and their dispatch.
+// block_fused.hip -- kernels of the fused small-block passes and their dispatch: the transform of all axes (block_core.h's phases) and the
+// plain roundtrip (block_rt.h's kernel).
 #include <hip/hip_runtime.h>
 #include "backend.h"
-#include "block_core.h"
+#include "block_rt.h"
 
 namespace dspfft {
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -22,42 +23,6 @@ __global__ void __launch_bounds__(BLOCK_THREADS) block_kernel(const BlockArgs a)
 	block_store_rows<NX, NY, NZ>(a, a.out, lds, bout, cnt, tid);
 }
 
-// motion's per-block pipeline in one pass: load (float / 8-bit), REDFT10 along x, y, z, filter, REDFT01 along z, y, x, store
-template <int NX, int NY, int NZ, bool IN8, bool OUT8>
-__global__ void __launch_bounds__(BLOCK_THREADS) block_roundtrip_kernel(const BlockRtArgs a)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-	__shared__ unsigned int wg_coded;
-	float *lds = reinterpret_cast<float *>(lds_raw);
-	const int tid = threadIdx.x;
-	if (tid == 0) wg_coded = 0;
-	long long bin, bout;
-	int cnt;
-	block_base(a, blockIdx.x, bin, bout, cnt);
-	block_load_x<NX, NY, NZ, KIND_REDFT10, IN8>(a, block_axis_args(a.f, 0, NY == 1 && NZ == 1), a.in, a.in8, lds, bin, cnt, tid);
-	__syncthreads();
-	// the last forward axis, the filter and the same axis of the inverse run on one line in registers (block_lines_mid)
-	unsigned long long mine = 0;
-	if constexpr (NZ > 1) {
-		if constexpr (NY > 1) { block_lines_y<NX, NY, NZ, KIND_REDFT10>(a, block_axis_args(a.f, 1, false), lds, cnt, tid); __syncthreads(); }
-		block_lines_mid<NX, NY, NZ, true>(a, block_axis_args(a.f, 2, true), block_axis_args(a.i, 2, false), a.filt, lds, cnt, tid, mine);
-		__syncthreads();
-		if constexpr (NY > 1) { block_lines_y<NX, NY, NZ, KIND_REDFT01>(a, block_axis_args(a.i, 1, false), lds, cnt, tid); __syncthreads(); }
-	} else {
-		block_lines_mid<NX, NY, NZ, false>(a, block_axis_args(a.f, 1, true), block_axis_args(a.i, 1, false), a.filt, lds, cnt, tid, mine);
-		__syncthreads();
-	}
-	if (a.filt.enabled && a.coded) {
-		unsigned int m = (unsigned int)mine;
-		for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
-		if ((tid & 63) == 0 && m) atomicAdd(&wg_coded, m);
-		__syncthreads();
-		if (tid == 0 && wg_coded) atomicAdd(a.coded, (unsigned long long)wg_coded);
-	}
-	// the inverse's global scale rides on its x pass, the last one here
-	block_store_x<NX, NY, NZ, KIND_REDFT01, OUT8>(a, block_axis_args(a.i, 0, true), a.out, a.out8, a.mul8, lds, bout, cnt, tid);
-}
-
 template <class K>
 static int allow64k(K kern)
 {
@@ -75,9 +40,9 @@ static int launch_block(const BlockArgs &a, int nwg, size_t lds, void *stream)
 template <int NX, int NY, int NZ, bool IN8, bool OUT8>
 static int launch_block_rt(const BlockRtArgs &a, int nwg, size_t lds, void *stream)
 {
-	static int attr = allow64k(block_roundtrip_kernel<NX, NY, NZ, IN8, OUT8>);
+	static int attr = allow64k(block_roundtrip_kernel<NX, NY, NZ, IN8, OUT8, BlockRtArgs>);
 	if (attr) return attr;
-	hipLaunchKernelGGL((block_roundtrip_kernel<NX, NY, NZ, IN8, OUT8>), dim3(nwg), dim3(BLOCK_THREADS), lds, (hipStream_t)stream, a);
+	hipLaunchKernelGGL((block_roundtrip_kernel<NX, NY, NZ, IN8, OUT8, BlockRtArgs>), dim3(nwg), dim3(BLOCK_THREADS), lds, (hipStream_t)stream, a);
 	HIPCHK(hipGetLastError());
 	return 0;
 }

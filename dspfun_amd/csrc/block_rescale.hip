@@ -1,11 +1,11 @@
 // block_rescale.hip -- motion -b with -s over a block grid (motion --blocksize 8x8x8 --size 4x4x4 and the like): the fused small-block
 // roundtrip whose inverse runs over other extents than its forward transform, every block of the grid in ONE launch.  The phases are
 // block_rs_core.h's; one kernel serves every pair of extents and every kind of end (float, 8-bit, 8-bit with motion --linear's tables),
-// each phase chosen by a switch that is uniform over the workgroup.  A translation unit of its own: the block == scaled kernels beside it
-// (block_fused.hip, block_topn.hip, block_trc.hip) are what they were.
+// each phase chosen by a switch that is uniform over the workgroup.  The table staging and the coded-count reduction are block_rt.h's.
 #include <hip/hip_runtime.h>
 #include "backend.h"
 #include "block_rs_core.h"
+#include "block_rt.h"
 
 namespace dspfft {
 
@@ -22,32 +22,17 @@ __global__ void __launch_bounds__(BLOCK_THREADS) block_rescale_kernel(const Bloc
 	long long bin, bout;
 	int cnt;
 	block_base(args, blockIdx.x, bin, bout, cnt);
-	double *thr = nullptr;
-	float *lut = nullptr;
-	if (args.tab_out && a.out8) {
-		thr = reinterpret_cast<double *>(behind);
-		for (int i = tid; i < 256; i += BLOCK_THREADS) thr[i] = args.tab_out->thr[i];
-	}
-	if (args.tab_in && a.in8) {
-		lut = reinterpret_cast<float *>(behind + sizeof(double) * 256);
-		for (int i = tid; i < 256; i += BLOCK_THREADS) lut[i] = args.tab_in->lut[i];
-		__syncthreads();          // the load reads the table
-	}
-	rs_phase_load(a, lds, bin, cnt, tid, lut);
+	// (an end that is not 8-bit has no table)
+	const BlockTrc t = block_trc_stage(a.in8 ? args.tab_in : nullptr, a.out8 ? args.tab_out : nullptr, args.trc_out, behind, tid);
+	rs_phase_load(a, lds, bin, cnt, tid, t.lut);
 	__syncthreads();
 	if (a.nz > 1) { rs_phase_fwd_y(a, lds, cnt, tid); __syncthreads(); }
 	unsigned long long mine = 0;
 	rs_phase_mid(a, lds, cnt, tid, mine);
 	__syncthreads();
 	if (a.nz > 1) { rs_phase_inv_y(a, lds, cnt, tid); __syncthreads(); }
-	if (a.filt.enabled && args.coded) {
-		unsigned int m = (unsigned int)mine;
-		for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
-		if ((tid & 63) == 0 && m) atomicAdd(wg_coded, m);
-		__syncthreads();
-		if (tid == 0 && *wg_coded) atomicAdd(args.coded, (unsigned long long)*wg_coded);
-	}
-	rs_phase_store(a, lds, bout, cnt, tid, thr, args.trc_out);
+	if (a.filt.enabled && args.coded) block_coded_add(mine, wg_coded, args.coded);
+	rs_phase_store(a, lds, bout, cnt, tid, t.thr, args.trc_out);
 }
 
 }  // namespace dspfft

@@ -77,24 +77,7 @@ DSP_HD void rs_load_x(const RsTile &a, const TinyArgs &tx, float *lds, long long
 		const int z = row >> ly, y = row & (a.ny - 1);
 		const long long off = bin + (long long)g * a.sxb_in + (long long)z * a.sz_in + (long long)y * a.sy_in;
 		float x[NX], o[NX];
-		if constexpr (U8) {
-#pragma unroll
-			for (int j = 0; j < NX / 4; j++) {
-				uint32_t w4;
-				__builtin_memcpy(&w4, a.in8 + off + 4 * j, 4);
-#pragma unroll
-				for (int q = 0; q < 4; q++) {
-					if constexpr (TRC) x[4 * j + q] = lut[(w4 >> (8 * q)) & 0xffu];
-					else x[4 * j + q] = (float)((w4 >> (8 * q)) & 0xffu);
-				}
-			}
-		} else {
-#pragma unroll
-			for (int j = 0; j < NX / 4; j++) {      // 16-byte aligned: the engine refuses other layouts
-				const float4 v = reinterpret_cast<const float4 *>(a.in + off)[j];
-				x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
-			}
-		}
+		block_line_read<NX, U8, TRC>(a.in, a.in8, off, lut, x);
 		tiny_dct<NX, KIND_REDFT10>(tx, x, o);
 		float4 *q = reinterpret_cast<float4 *>(lds + (z * my + y) * a.pitch + g * a.tw);
 #pragma unroll
@@ -123,21 +106,7 @@ DSP_HD void rs_store_x(const RsTile &a, const TinyArgs &tx, const float *lds, lo
 			x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
 		}
 		tiny_dct<SX, KIND_REDFT01>(tx, x, o);
-		if constexpr (U8) {
-#pragma unroll
-			for (int j = 0; j < SX / 4; j++) {
-				uint32_t w4 = 0;
-#pragma unroll
-				for (int k = 0; k < 4; k++) {
-					if constexpr (TRC) { const double pel = (double)o[4 * j + k] * a.mul8; w4 |= trc_u8_byte_from(thr, pel, trc_u8_seed(tp, pel)) << (8 * k); }
-					else w4 |= quantise_u8_of(o[4 * j + k], a.mul8, (float)a.mul8) << (8 * k);
-				}
-				__builtin_memcpy(a.out8 + off + 4 * j, &w4, 4);
-			}
-		} else {
-#pragma unroll
-			for (int j = 0; j < SX / 4; j++) { float4 v; v.x = o[4 * j]; v.y = o[4 * j + 1]; v.z = o[4 * j + 2]; v.w = o[4 * j + 3]; reinterpret_cast<float4 *>(a.out + off)[j] = v; }
-		}
+		block_line_write<SX, U8, TRC>(o, a.out, a.out8, off, a.mul8, thr, tp);
 	}
 }
 

@@ -1,6 +1,6 @@
-// block_trc.hip -- the fused small-block roundtrip of 8-bit video with motion --linear (dspfft_plan_set_u8_trc): block_fused.hip's and
-// block_topn.hip's kernels (the bodies are block_rt.h's) with the transfer characteristic's decode table at the load and its threshold table
-// at the store, both in LDS behind the tile (3 KB).  A translation unit of its own: the plain kernels beside it are what they were.
+// block_trc.hip -- the fused small-block roundtrip of 8-bit video with motion --linear (dspfft_plan_set_u8_trc): block_rt.h's two kernels
+// on BlockRtTrcArgs, with the transfer characteristic's decode table at the load and its threshold table at the store, both in LDS behind
+// the tile (3 KB), and their dispatch.
 #include <hip/hip_runtime.h>
 #include "backend.h"
 #include "block_rt.h"
@@ -10,20 +10,19 @@ namespace dspfft {
 // OUT8 = false: the dithered roundtrip, whose bytes the dither kernel stores from the float result (no call combines it with a coefficient
 // limit: that pair is not instantiated)
 template <int NX, int NY, int NZ, bool OUT8, bool TOPN>
-__global__ void __launch_bounds__(BLOCK_THREADS) block_roundtrip_trc_kernel(const BlockRtTrcArgs a)
+static auto block_trc_kernel()
 {
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-	__shared__ unsigned int wg_coded;
-	if constexpr (TOPN) block_roundtrip_topn_body<NX, NY, NZ, true, OUT8, true>(a, &a, lds_raw, wg_coded);
-	else block_roundtrip_body<NX, NY, NZ, true, OUT8, true>(a, &a, lds_raw, wg_coded);
+	if constexpr (TOPN) return &block_roundtrip_topn_kernel<NX, NY, NZ, true, OUT8, BlockRtTrcArgs>;
+	else return &block_roundtrip_kernel<NX, NY, NZ, true, OUT8, BlockRtTrcArgs>;
 }
 
 template <int NX, int NY, int NZ, bool OUT8, bool TOPN>
 static int launch_block_rt_trc(const BlockRtTrcArgs &a, int nwg, size_t lds, void *stream)
 {
-	static int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void *>(block_roundtrip_trc_kernel<NX, NY, NZ, OUT8, TOPN>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+	const auto kern = block_trc_kernel<NX, NY, NZ, OUT8, TOPN>();
+	static int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
 	if (attr) return attr;
-	hipLaunchKernelGGL((block_roundtrip_trc_kernel<NX, NY, NZ, OUT8, TOPN>), dim3(nwg), dim3(BLOCK_THREADS), lds, (hipStream_t)stream, a);
+	hipLaunchKernelGGL(kern, dim3(nwg), dim3(BLOCK_THREADS), lds, (hipStream_t)stream, a);
 	return (int)hipGetLastError();
 }
 

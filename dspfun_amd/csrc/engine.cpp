@@ -1798,7 +1798,7 @@ struct RtCall {
 	U8Trc trc_in, trc_out;                // dspfft_plan_set_u8_trc of the forward plan (8-bit input) and of the inverse plan (8-bit or dithered output)
 	bool dithered;                        // set by roundtrip_core before rt_check: the bytes come from the dither kernel
 	bool grid;                            // a rescaled block grid (rt_grid): block_rescale.hip's kernel runs the call, out of place
-	BlockRsArgs rs;                       // its geometry, derived for the pair
+	BlockRsArgs rs;                       // its arguments, with the geometry derived for the pair
 	int rs_nwg; size_t rs_lds;
 };
 // the conversions at the ends of the unfused paths, plain or through the call's transfer characteristic
@@ -1809,6 +1809,41 @@ int rt_u8_in(const RtCall &c, float *dst, uint64_t len)
 int rt_u8_out(const RtCall &c, const float *src, uint64_t len)
 {
 	return c.trc_out.id ? dspfft_u8_trc_flat_launch(c.d_out8, src, c.mul8, len, 1, c.trc_out.id, c.trc_out.tab, c.stream) : be_f32_to_u8(c.d_out8, src, c.mul8, len, c.stream);
+}
+
+// ---- what rt_check and rt_grid both ask of a call ----
+// the filter's parameters, checked, as the kernels take them (c.mf all zero: no filter)
+int rt_filter(RtCall &c)
+{
+	memset(&c.mf, 0, sizeof c.mf);
+	if (!c.fp) return 0;
+	if (c.fp->preserve_dc < 0 || c.fp->preserve_dc > 2 || c.fp->minbuf_hw[0] < 1 || c.fp->minbuf_hw[1] < 1 || c.fp->block_depth < 1) return fail(-1, "bad filter parameters");
+	motion_filter_of(*c.fp, c.mf);
+	return 0;
+}
+// motion --linear: a plan's transfer characteristic acts where the call has an 8-bit end for it
+void rt_trc_ends(RtCall &c)
+{
+	if (c.d_in8 && c.fwd->u8_trc) c.trc_in = U8Trc{c.fwd->u8_trc, c.fwd->u8_tab};
+	if ((c.d_out8 || c.dithered) && c.inv->u8_trc) c.trc_out = U8Trc{c.inv->u8_trc, c.inv->u8_tab};
+}
+// the fused block kernels move float4s and packed words of four bytes at the two ends
+bool rt_ends_aligned(const RtCall &c)
+{
+	const uintptr_t pin = c.d_in8 ? (uintptr_t)c.d_in8 : (uintptr_t)c.d_in, pout = c.d_out8 ? (uintptr_t)c.d_out8 : (uintptr_t)c.d_out;
+	return !((c.d_in8 ? 3u : 15u) & pin) && !((c.d_out8 ? 3u : 15u) & pout);
+}
+// The arguments every fused block roundtrip shares: the forward plan's geometry with the inverse plan's output strides spliced in, the
+// call's buffers, the two plans' scales, the filter (rt_filter has run) and the counter.
+void rt_block_args(const RtCall &c, BlockRtArgs &a)
+{
+	static_cast<BlockGeom &>(a) = c.fwd->blk;
+	const BlockGeom &o = c.inv->blk;
+	a.sy_out = o.sy_out; a.sz_out = o.sz_out; a.sxb_out = o.sxb_out;
+	for (int d = 0; d < o.nd; d++) a.bos[d] = o.bos[d];
+	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
+	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
+	a.filt = c.mf; a.coded = c.coded;
 }
 
 // motion -b with -s over a block grid (motion.c:488-499,535-552): both plans cut their volumes into small blocks, `fwd` the input volume
@@ -1833,25 +1868,18 @@ int rt_grid(RtCall &c)
 	for (int d = 0; same && d < f.nd; d++) same = f.bn[d] == i.bn[d];
 	if (!same || fwd->howmany != inv->howmany) return fail(-2, "%s: the plans count different numbers of blocks", what);
 	if (!dspfft_block_rescale_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale.hip)", what);
-	BlockRsArgs &r = c.rs;
-	memset(&r, 0, sizeof r);
-	static_cast<BlockGeom &>(r) = f;
-	r.sy_out = i.sy_out; r.sz_out = i.sz_out; r.sxb_out = i.sxb_out;
-	for (int d = 0; d < i.nd; d++) r.bos[d] = i.bos[d];
-	r.ox = i.nx; r.oy = i.ny; r.oz = i.nz;
 	const int mx = std::max(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
 	if (c.keep && c.keep < (size_t)mx * my * mz)
 		return fail(-2, "%s: a coefficient limit is not implemented here (the reference selects over the whole embedding, motion.c:652-668)", what);
 	c.keep = 0;
-	const uintptr_t pin = c.d_in8 ? (uintptr_t)c.d_in8 : (uintptr_t)c.d_in, pout = c.d_out8 ? (uintptr_t)c.d_out8 : (uintptr_t)c.d_out;
-	if (((c.d_in8 ? 3u : 15u) & pin) || ((c.d_out8 ? 3u : 15u) & pout)) return fail(-2, "%s: float buffers must be 16-byte aligned, 8-bit buffers 4-byte aligned", what);
-	memset(&c.mf, 0, sizeof c.mf);
-	if (c.fp) {
-		if (c.fp->preserve_dc < 0 || c.fp->preserve_dc > 2 || c.fp->minbuf_hw[0] < 1 || c.fp->minbuf_hw[1] < 1 || c.fp->block_depth < 1) return fail(-1, "bad filter parameters");
-		motion_filter_of(*c.fp, c.mf);
-	}
-	if (c.d_in8 && fwd->u8_trc) c.trc_in = U8Trc{fwd->u8_trc, fwd->u8_tab};
-	if ((c.d_out8 || c.dithered) && inv->u8_trc) c.trc_out = U8Trc{inv->u8_trc, inv->u8_tab};
+	if (!rt_ends_aligned(c)) return fail(-2, "%s: float buffers must be 16-byte aligned, 8-bit buffers 4-byte aligned", what);
+	if (int rc = rt_filter(c)) return rc;
+	rt_trc_ends(c);
+	BlockRsArgs &r = c.rs;
+	memset(&r, 0, sizeof r);
+	rt_block_args(c, r);
+	r.ox = i.nx; r.oy = i.ny; r.oz = i.nz;
+	r.tab_in = (const TrcU8Tab *)c.trc_in.tab; r.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; r.trc_out = c.trc_out.id;
 	// blocks per workgroup: build_block's rule on the embedding with tiles of twice the size -- about 8192 samples (32 KB), rows of at most
 	// 1 KB.  The pruned phases have min(block, scaled) columns per block, so build_block's 4096 samples leave half the workgroup idle in them
 	// (1920x1080x64, 8-bit: 8x8x8 -> 4x4x4 1.17 -> 1.43 TB/s, 16x16x16 -> 8x8x8 0.92 -> 1.29, profiles/r09_motion_block_rescale.txt).  The
@@ -1877,12 +1905,7 @@ int rt_grid(RtCall &c)
 // into the inverse plan's output layout
 int rt_run_grid(const RtCall &c)
 {
-	BlockRsArgs a = c.rs;
-	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
-	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
-	a.filt = c.mf; a.coded = c.coded;
-	a.tab_in = (const TrcU8Tab *)c.trc_in.tab; a.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; a.trc_out = c.trc_out.id;
-	if (int rc = dspfft_block_rescale_launch(&a, c.rs_nwg, c.rs_lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid): backend code %d", rc);
+	if (int rc = dspfft_block_rescale_launch(&c.rs, c.rs_nwg, c.rs_lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid): backend code %d", rc);
 	return 0;
 }
 
@@ -1916,11 +1939,7 @@ int rt_check(RtCall &c)
 	if (fwd->batches.size() != inv->batches.size()) return fail(-1, "roundtrip: batch layouts differ");
 	for (size_t b = 0; b < fwd->batches.size(); b++)
 		if (fwd->batches[b].n != inv->batches[b].n || fwd->batches[b].os != inv->batches[b].is || inv->batches[b].is != inv->batches[b].os) return fail(-1, "roundtrip: batch layouts differ");
-	memset(&c.mf, 0, sizeof c.mf);
-	if (fp) {
-		if (fp->preserve_dc < 0 || fp->preserve_dc > 2 || fp->minbuf_hw[0] < 1 || fp->minbuf_hw[1] < 1 || fp->block_depth < 1) return fail(-1, "bad filter parameters");
-		motion_filter_of(*fp, c.mf);
-	}
+	if (int rc = rt_filter(c)) return rc;
 	// (the filter addresses the working buffer with 32-bit offsets)
 	c.span = 1;
 	for (int a = 0; a < fwd->rank; a++) c.span += (long long)(std::max(fwd->n[a], inv->n[a]) - 1) * fwd->axes[a].os;
@@ -1931,13 +1950,10 @@ int rt_check(RtCall &c)
 		const int k = 3 - fwd->rank + a;
 		c.nf3[k] = fwd->n[a]; c.ni3[k] = inv->n[a]; c.sw3[k] = fwd->axes[a].os; c.si3[k] = fwd->axes[a].is;
 	}
-	const uintptr_t pin = c.d_in8 ? (uintptr_t)c.d_in8 : (uintptr_t)c.d_in, pout = c.d_out8 ? (uintptr_t)c.d_out8 : (uintptr_t)c.d_out;
-	c.block = !c.rescale && block_roundtrip_ok(fwd, inv) && !((c.d_in8 ? 3u : 15u) & pin) && !((c.d_out8 ? 3u : 15u) & pout);
+	c.block = !c.rescale && block_roundtrip_ok(fwd, inv) && rt_ends_aligned(c);
 	c.u8_first = pass_has_u8(fwd, fwd->passes[0]);
 	c.u8_last = pass_has_u8(inv, inv->passes[ni - 1]);
-	// motion --linear: a plan's transfer characteristic acts where the call has an 8-bit end for it
-	if (c.d_in8 && fwd->u8_trc) c.trc_in = U8Trc{fwd->u8_trc, fwd->u8_tab};
-	if ((c.d_out8 || c.dithered) && inv->u8_trc) c.trc_out = U8Trc{inv->u8_trc, inv->u8_tab};
+	rt_trc_ends(c);
 	if (c.trc_in.id || c.trc_out.id) {
 		if (!dspfft_u8_trc_flat_launch || !dspfft_u8_trc_region_launch || !dspfft_dither_trc_launch || !dspfft_block_trc_launch || !dspfft_row_u8_trc_launch)
 			return fail(-3, "8-bit roundtrip with a transfer characteristic: not built into this library (the kernels are HIP-only)");
@@ -1983,13 +1999,7 @@ int rt_check(RtCall &c)
 int rt_run_block(const RtCall &c)
 {
 	BlockRtArgs a;
-	static_cast<BlockGeom &>(a) = c.fwd->blk;
-	const BlockGeom &o = c.inv->blk;
-	a.sy_out = o.sy_out; a.sz_out = o.sz_out; a.sxb_out = o.sxb_out;
-	for (int d = 0; d < o.nd; d++) a.bos[d] = o.bos[d];
-	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
-	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
-	a.filt = c.mf; a.coded = c.coded;
+	rt_block_args(c, a);
 	if (c.trc_in.id || c.trc_out.id) {
 		BlockRtTrcArgs t;
 		static_cast<BlockRtArgs &>(t) = a;

@@ -361,8 +361,8 @@ def test_dithered_block_roundtrip_takes_the_function(gpu):
 @pytest.mark.parametrize("keep", [0, 5])
 def test_the_identity_function_gives_the_plain_kernels_bytes_and_counts(gpu, keep):
     """trc `linear` is the identity: its decode table is the byte itself and its thresholds are the half-integers, so the kernels with tables
-    must give what the plain kernels give -- bytes and the count of coded coefficients.  The block kernels with tables repeat the plain
-    kernels' sequence of phases in a unit of their own (block_rt.h); this is what holds the two in step."""
+    must give what the plain kernels give -- bytes and the count of coded coefficients.  The block kernels with tables are the plain
+    kernels' sequence of phases (block_rt.h) with TRC = true."""
     block, (D, H, W) = (8, 8, 8), (16, 32, 64)
     pix = ol.synth_u8(0x8B1A, D * H * W).reshape(D, H, W)
     flt = dict(active=block, minbuf_hw=(8, 8), block_depth=8, band_begin=(0, 1, 0), band_end=(8, 8, 7), damp=0.5, boost=1.25, preserve_dc=1, quantizer=3.0)
