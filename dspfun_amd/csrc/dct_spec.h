@@ -1046,6 +1046,7 @@ struct ColSpecT {
 		LC pre[(Y_ROUNDS > 2 * K_ROUNDS) ? Y_ROUNDS : 2 * K_ROUNDS];
 		CX tw[1];
 	};
+	struct StateMid { LC pre[2 * K_ROUNDS]; };      // what mid_read hands mid_write (spec_fused.h: one state object per transform)
 	template <class ST, class F>
 	static DSP_HD void mid_read(const PA &af, const PA &ai, const V *buf, long long bout, int tid, ST &st, const F &filt, unsigned long long &coded)
 	{

@@ -2055,6 +2055,24 @@ int rt_run_rescale(const RtCall &c)
 	return 0;
 }
 
+// Whether rt_run_passes runs the forward plan's last pass and the inverse plan's first as ONE column kernel, and that kernel's arguments: both
+// are COL passes with the same listed kernel (or kernels compiled at plan time for the same type) over the same tiles, plain, without a host
+// loop, on 16-byte-aligned buffers, and nothing has to see the whole spectrum in between.  `src` is what the forward plan's last pass reads.
+bool rt_col_fused(const RtCall &c, const float *src, PassArgs &af, PassArgs &ai, bool &compiled)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const Pass &F = *c.F, &I = *c.I;
+	const bool listed = F.has_spec && I.has_spec && F.spec.id == I.spec.id;
+	compiled = !listed && F.jit && I.jit && F.jit_fn_rt && F.jit_type == I.jit_type;      // kernels compiled at plan time (jit_kernels.h)
+	const bool fusable = F.type == Pass::COL && I.type == Pass::COL && (listed || compiled) && F.spec_nwg == I.spec_nwg &&
+	                     F.hostloop.empty() && I.hostloop.empty() && (15u & ((uintptr_t)src | (uintptr_t)c.d_out)) == 0 && !fused_roundtrip_off() &&
+	                     !c.keep;             // (the selection needs every coefficient of a block before the filter sees one)
+	if (!fusable) return false;
+	fill_args(af, F.spa, fwd, F, src, c.d_out, fwd->scale, Fuse());
+	fill_args(ai, I.spa, inv, I, (const float *)c.d_out, c.d_out, inv->passes.size() == 1 ? inv->scale : 1.0, Fuse());
+	return is_plain_args(af) && is_plain_args(ai);      // (the fused kernel is the plain instantiation of both passes)
+}
+
 // the plans' pass lists, with the forward plan's last and the inverse plan's first pass in one column kernel where there is one
 int rt_run_passes(const RtCall &c)
 {
@@ -2079,17 +2097,9 @@ int rt_run_passes(const RtCall &c)
 		if (int rc = run_pass<float>(fwd, P, P.first ? d_in : d_out, d_out, false, stream)) return rc;
 	}
 	const float *src = nf == 1 ? d_in : d_out;
-	const bool listed = F.has_spec && I.has_spec && F.spec.id == I.spec.id;
-	const bool compiled = !listed && F.jit && I.jit && F.jit_fn_rt && F.jit_type == I.jit_type;      // kernels compiled at plan time (jit_kernels.h)
-	const bool fusable = F.type == Pass::COL && I.type == Pass::COL && (listed || compiled) && F.spec_nwg == I.spec_nwg &&
-	                     F.hostloop.empty() && I.hostloop.empty() && (15u & ((uintptr_t)src | (uintptr_t)d_out)) == 0 && !fused_roundtrip_off() &&
-	                     !c.keep;             // (the selection needs every coefficient of a block before the filter sees one)
 	PassArgs af, ai;
-	if (fusable) {
-		fill_args(af, F.spa, fwd, F, src, d_out, fwd->scale, Fuse());
-		fill_args(ai, I.spa, inv, I, (const float *)d_out, d_out, ni == 1 ? inv->scale : 1.0, Fuse());
-	}
-	if (fusable && is_plain_args(af) && is_plain_args(ai)) {      // (the fused kernel is the plain instantiation of both passes)
+	bool compiled;
+	if (rt_col_fused(c, src, af, ai, compiled)) {
 		if (compiled) {
 			// parameters: (PassArgs af, PassArgs ai, FilterOp filt, unsigned long long *coded); FilterOp is the MotionFilter, nothing else
 			void *args[4] = {&af, &ai, (void *)&c.mf, (void *)&c.coded};
@@ -2372,8 +2382,49 @@ struct ChanLinesGuard {
 	}
 	~ChanLinesGuard() { if (on) g_chan_lines_suspended--; }
 };
+// ---- forward/inverse pairs of a batch as one roundtrip ----
+// Items i, i + 1 of a batch -- a forward plan, then its inverse in place on the forward's output, on the same stream -- are one roundtrip call
+// without a filter: where rt_run_passes would run that call's two middle passes as one column kernel (rt_col_fused), the pair runs through it,
+// the spectrum between the two column passes is never stored and the frame is swept three times instead of four.  The fused kernel is bit-identical
+// to the pair pass by pass, so which repeats fuse (the timed ones do not: their passes are bracketed one by one) cannot be seen in the results.
+// Checked once per call, not once per repeat: `calls[i]` is the checked call of the pair that begins at item i (fwd == NULL: none).
+static std::atomic<unsigned long long> g_many_fused_pairs{0};
+extern "C" unsigned long long dspfft_many_fused_pairs(void) { return g_many_fused_pairs.load(std::memory_order_relaxed); }
+
+struct ManyPairs { std::vector<RtCall> calls; };
+static bool many_pair_check(const dspfft_plan *plans, const void *const *d_in, void *const *d_out, void *const *streams, int i, RtCall &c)
+{
+	const dspfft_plan fwd = plans[i], inv = plans[i + 1];
+	if (fwd->f64 || inv->f64 || (streams && streams[i] != streams[i + 1]) || d_out[i] != d_in[i + 1] || d_in[i + 1] != d_out[i + 1]) return false;
+	// what dspfft_execute would run must be the plans' plain pass lists, which are what the roundtrip runs
+	if (fwd->has_block || inv->has_block || &pick_passes(fwd, d_in[i], d_out[i]) != &fwd->passes || &pick_passes(inv, d_in[i + 1], d_out[i + 1]) != &inv->passes) return false;
+	if (fwd->passes.empty() || inv->passes.empty()) return false;
+	c = RtCall{fwd, inv, (const float *)d_in[i], (float *)d_out[i], nullptr, nullptr, 1.0, nullptr, nullptr, streams ? streams[i] : nullptr, 0, nullptr, 0};
+	char err[sizeof g_err];
+	memcpy(err, g_err, sizeof err);                  // a pair that is none is no error of the batch
+	const bool ok = rt_check(c) == 0 && !c.grid && !c.block && !c.rescale;
+	memcpy(g_err, err, sizeof err);
+	if (!ok) return false;
+	PassArgs af, ai;
+	bool compiled;
+	return rt_col_fused(c, fwd->passes.size() == 1 ? c.d_in : c.d_out, af, ai, compiled);
+}
+static void many_pairs_find(int count, const dspfft_plan *plans, const void *const *d_in, void *const *d_out, void *const *streams, ManyPairs &mp)
+{
+	mp.calls.clear();
+	if (count < 2 || fused_roundtrip_off()) return;
+	mp.calls.resize((size_t)count);
+	bool any = false;
+	for (int i = 0; i + 1 < count; i++) {
+		RtCall c;
+		if (many_pair_check(plans, d_in, d_out, streams, i, c)) { mp.calls[i] = c; any = true; } else mp.calls[i].fwd = nullptr;
+	}
+	mp.calls[count - 1].fwd = nullptr;
+	if (!any) mp.calls.clear();
+}
+
 static int execute_many_once(int count, const dspfft_plan *plans, const void *const *d_in, void *const *d_out, void *const *streams,
-                             int timed_item, int timed_count, void *const *pass_events)
+                             int timed_item, int timed_count, void *const *pass_events, const ManyPairs &mp)
 {
 	ChanLinesGuard guard(count, plans, streams);
 	int ev = 0;
@@ -2381,6 +2432,13 @@ static int execute_many_once(int count, const dspfft_plan *plans, const void *co
 		dspfft_plan pl = plans[i];
 		void *st = streams ? streams[i] : nullptr;
 		const bool timed = pass_events && i >= timed_item && i < timed_item + timed_count;
+		// left to right, an item in one pair at most; a timed window that covers either item splits the pair
+		if (!mp.calls.empty() && mp.calls[i].fwd && !timed && !(pass_events && i + 1 >= timed_item && i + 1 < timed_item + timed_count)) {
+			if (int rc = rt_run_passes(mp.calls[i])) return rc;
+			g_many_fused_pairs.fetch_add(1, std::memory_order_relaxed);
+			i++;
+			continue;
+		}
 		const int rc = pl->f64 ? execute_item<double>(pl, d_in[i], d_out[i], st, timed, pass_events, ev) : execute_item<float>(pl, d_in[i], d_out[i], st, timed, pass_events, ev);
 		if (rc) return rc;
 	}
@@ -2416,7 +2474,9 @@ extern "C" int dspfft_execute_many(int count, const dspfft_plan *plans, const fl
                                    int timed_item, int timed_count, void *const *pass_events)
 {
 	if (int rc = check_many(count, plans, (const void *const *)d_in, (void *const *)d_out, streams, timed_item, timed_count, pass_events != nullptr, false)) return rc;
-	return execute_many_once(count, plans, (const void *const *)d_in, (void *const *)d_out, streams, timed_item, timed_count, pass_events);
+	ManyPairs mp;
+	many_pairs_find(count, plans, (const void *const *)d_in, (void *const *)d_out, streams, mp);
+	return execute_many_once(count, plans, (const void *const *)d_in, (void *const *)d_out, streams, timed_item, timed_count, pass_events, mp);
 }
 
 // The frame loop of a clip inside the library: the batch `repeats` times (motion/motion.c:613-753 runs its per-frame plans once per
@@ -2434,6 +2494,8 @@ extern "C" int dspfft_execute_many_repeat(int count, const dspfft_plan *plans, c
 	std::vector<void *> join;
 	const bool rejoin = rejoin_every > 0 && uniq.size() > 1;
 	if (rejoin) for (size_t i = 0; i < uniq.size(); i++) { void *e = be_order_event_create(); if (!e) { for (void *x : join) be_event_destroy(x); return fail(-4, "event creation failed"); } join.push_back(e); }
+	ManyPairs mp;
+	if (repeats > 0) many_pairs_find(count, plans, d_in, d_out, streams, mp);
 	int rc = 0, windows = 0;
 	size_t ev_off = 0;
 	for (int k = 0; k < repeats && !rc; k++) {
@@ -2447,10 +2509,10 @@ extern "C" int dspfft_execute_many_repeat(int count, const dspfft_plan *plans, c
 		}
 		if (ev && k % timed_every == 0) {
 			const int first = (int)(((long long)windows * timed_count) % count);
-			rc = execute_many_once(count, plans, d_in, d_out, streams, first, timed_count, pass_events + ev_off);
+			rc = execute_many_once(count, plans, d_in, d_out, streams, first, timed_count, pass_events + ev_off, mp);
 			for (int i = first; i < first + timed_count; i++) ev_off += 2 * pick_passes(plans[i], d_in[i], d_out[i]).size();    // (alignment of the pointers only)
 			windows++;
-		} else rc = execute_many_once(count, plans, d_in, d_out, streams, 0, 0, nullptr);
+		} else rc = execute_many_once(count, plans, d_in, d_out, streams, 0, 0, nullptr, mp);
 	}
 	for (void *x : join) be_event_destroy(x);
 	return rc;

@@ -53,41 +53,51 @@ __device__ __forceinline__ void col_roundtrip_body(unsigned char *lds, const typ
 	typename S::V *buf = reinterpret_cast<typename S::V *>(lds);
 	const int tid = threadIdx.x;
 	if (tid == 0) wg_coded = 0;
-	typename S::StateRT st;
 	long long bin, bout;
 	S::base(af, blockIdx.x, bin, bout);
 	bool hit = false;
 	DSP_STAMP(0);
-	S::template prefetch<KIND_REDFT10>(af, bin, tid, st, hit);
-	S::template phase<KIND_REDFT10, 0>(af, buf, bout, tid, st);
-	__syncthreads();
-	DSP_STAMP(1);
-	// The empty asm statements make the thread index (and, below, the inverse plan's table pointers) opaque at each
-	// phase: otherwise index arithmetic and twiddle loads of LATER phases are hoisted to the top of the kernel and
-	// stay live across every barrier (measured: 176 VGPRs -> 1 workgroup per CU; with them: <= 128).
-	static_for<1, S::NS + 2>([&](auto ph) {
-		int t = tid; asm volatile("" : "+v"(t));
-		S::template phase<KIND_REDFT10, ph>(af, buf, bout, t, st);
+	// One state object per transform, each in a scope of its own.  A thread writes and reads its slots under run-time conditions on the
+	// (opaque) thread index, so in ONE object for the whole kernel the slots a condition leaves untouched carry the previous transform's
+	// values: the forward's last butterfly (x) stayed live to the inverse's last phase and the loaded rows (pre) to mid_write -- about 100
+	// registers across every barrier on the 2160 x 8 tile (128 VGPRs, 36 of them spilled).  A fresh object starts undefined instead.
+	{
+		typename S::template State<KIND_REDFT10> st;
+		S::template prefetch<KIND_REDFT10>(af, bin, tid, st, hit);
+		S::template phase<KIND_REDFT10, 0>(af, buf, bout, tid, st);
 		__syncthreads();
-		DSP_STAMP(1 + ph);
-	});
-	unsigned long long mine = 0;
-	int t = tid; asm volatile("" : "+v"(t));
-	S::mid_read(af, ai, buf, bout, t, st, filt, mine);
-	if (coded) {
-		unsigned int m = (unsigned int)mine;
-		for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
-		if ((tid & 63) == 0 && m) atomicAdd(&wg_coded, m);
+		DSP_STAMP(1);
+		// The empty asm statements make the thread index (and, below, the inverse plan's table pointers) opaque at each
+		// phase: otherwise index arithmetic and twiddle loads of LATER phases are hoisted to the top of the kernel and
+		// stay live across every barrier (measured: 176 VGPRs -> 1 workgroup per CU; with them: <= 128).
+		static_for<1, S::NS + 2>([&](auto ph) {
+			int t = tid; asm volatile("" : "+v"(t));
+			S::template phase<KIND_REDFT10, ph>(af, buf, bout, t, st);
+			__syncthreads();
+			DSP_STAMP(1 + ph);
+		});
 	}
-	__syncthreads();
-	DSP_STAMP(10);
-	if (coded && tid == 0 && wg_coded) atomicAdd(coded, (unsigned long long)wg_coded);
-	asm volatile("" : "+v"(t));
-	S::mid_write(buf, t, st);
-	__syncthreads();
-	DSP_STAMP(11);
+	int t = tid; asm volatile("" : "+v"(t));
+	{
+		typename S::StateMid st;
+		unsigned long long mine = 0;
+		S::mid_read(af, ai, buf, bout, t, st, filt, mine);
+		if (coded) {
+			unsigned int m = (unsigned int)mine;
+			for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
+			if ((tid & 63) == 0 && m) atomicAdd(&wg_coded, m);
+		}
+		__syncthreads();
+		DSP_STAMP(10);
+		if (coded && tid == 0 && wg_coded) atomicAdd(coded, (unsigned long long)wg_coded);
+		asm volatile("" : "+v"(t));
+		S::mid_write(buf, t, st);
+		__syncthreads();
+		DSP_STAMP(11);
+	}
 	typename S::PA a2 = ai;
 	asm volatile("" : "+s"(a2.W), "+s"(a2.T), "+s"(a2.out));
+	typename S::template State<KIND_REDFT01> st;
 	static_for<1, S::NPH>([&](auto ph) {
 		asm volatile("" : "+v"(t));
 		S::template phase<KIND_REDFT01, ph>(a2, buf, bout, t, st);

@@ -583,6 +583,11 @@ class Events:
             pass
 
 
+def many_fused_pairs(lib=None):
+    """dspfft_many_fused_pairs: forward/inverse pairs that Batch.run / run_repeat have run as one roundtrip so far in this process"""
+    return int((lib or _lib.load()).dspfft_many_fused_pairs())
+
+
 class Batch:
     """A fixed list of executions -- (plan, d_in, d_out, stream) per item -- enqueued by ONE call of dspfft_execute_many: the
     per-frame loop of motion (motion/motion.c:613-753) or of a clip of spec/ispec frames, without a binding-layer call per frame."""

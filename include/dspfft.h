@@ -75,6 +75,20 @@ int dspfft_execute_many(int count, const dspfft_plan *plans, const float *const 
  * Items may be f32 or f64 plans: each item's buffers are float or double as its plan says (hence the void pointers). */
 int dspfft_execute_many_repeat(int count, const dspfft_plan *plans, const void *const *d_in, void *const *d_out, void *const *hip_streams,
                                int repeats, int rejoin_every, int timed_every, int timed_count, void *const *pass_events);
+/* Forward/inverse pairs.  Both calls above may run two adjacent items i, i + 1 as ONE roundtrip (what dspfft_execute_roundtrip runs without
+ * a filter) when all of this holds: both plans are f32; hip_streams[i] == hip_streams[i + 1]; the second item works in place on the first
+ * one's output, d_out[i] == d_in[i + 1] == d_out[i + 1] (the first item may be in place or not); neither item lies in a timed window of
+ * that repeat (timed items always run pass by pass, two events per pass); plans[i] is REDFT10 and plans[i + 1] REDFT01 on every axis over
+ * the same layout, and the forward plan's last pass and the inverse plan's first (dspfft_plan_many_r2r_ordered(..., 1)) are column passes
+ * along the same axis with the same specialised kernel -- listed, or compiled at plan time -- over the same tiles, without a host loop,
+ * input window, modulation or alternating sign, on 16-byte-aligned buffers.  Those two passes then run as one kernel that keeps each tile in
+ * LDS between them: the spectrum after the forward plan's last pass is NEVER STORED (the buffer holds the forward plan's earlier passes'
+ * output until the roundtrip's own last passes overwrite it), which nothing ordered on that stream can observe.  The results are
+ * bit-identical to the two items run pass by pass.  Items are scanned left to right and belong to one pair at most ((fwd, inv, fwd) pairs
+ * the first two); a pair that fails any condition runs as two items, never as an error.  DSPFFT_NO_FUSED_ROUNDTRIP=1 (read per call)
+ * turns the pairing off.
+ * dspfft_many_fused_pairs: how many pairs this process has run that way so far (atomic, never reset). */
+unsigned long long dspfft_many_fused_pairs(void);
 /* Streams of the library's own for the calls above: plain non-blocking HIP streams (hipStreamCreateWithFlags(hipStreamNonBlocking)),
  * for hosts without a HIP binding of their own (cgo, ctypes ...) and for hosts whose framework hands out streams from a pool:
  * two streams of torch's pool were seen sharing a hardware queue, which serialises the two frames they carry (48K instead of 56K
