@@ -17,6 +17,8 @@ SYMBOLS = [
     "dspfft_plan_many_r2r", "dspfft_plan_r2r_2d", "dspfft_plan_set_scale", "dspfft_plan_set_axis_scale0",
     "dspfft_plan_many_r2r_f64", "dspfft_plan_set_scale_f64", "dspfft_plan_set_axis_scale0_f64", "dspfft_execute_f64", "dspfft_execute_masked_accumulate_f64", "dspfft_plan_scan_prepare", "dspfft_plan_set_input_window", "dspfft_plan_set_output_alternate", "dspfft_set_plan_effort", "dspfft_get_plan_effort",
     "dspfft_plan_many_r2r_ordered", "dspfft_plan_guru_r2r", "dspfft_execute_roundtrip", "dspfft_execute_roundtrip_u8", "dspfft_execute_roundtrip_u8_dither",
+    "dspfft_execute_spectrogram_u8", "dspfft_execute_spectrogram_f32", "dspfft_execute_ispectrogram_u8", "dspfft_execute_ispectrogram_f32",
+    "dspfft_motion_spec_blocks_u8", "dspfft_motion_spec_blocks_f32", "dspfft_motion_ispec_blocks_u8", "dspfft_motion_ispec_blocks_f32",
     "dspfft_roundtrip_topn_work_bytes", "dspfft_execute_roundtrip_topn", "dspfft_execute_roundtrip_u8_topn", "dspfft_motion_topn_blocks_work_bytes", "dspfft_motion_topn_blocks",
     "dspfft_execute", "dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
     "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_many_fused_pairs", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_execute_n", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
@@ -60,6 +62,11 @@ class MotionFilterParams(C.Structure):
     _fields_ = [("active", C.c_int * 3), ("minbuf_hw", C.c_int * 2), ("block_depth", C.c_int), ("band_begin", C.c_int * 3), ("band_end", C.c_int * 3),
                 ("damp", C.c_float), ("boost", C.c_float), ("threshold_lo", C.c_float), ("threshold_hi", C.c_float),
                 ("preserve_dc", C.c_int), ("grey_add", C.c_float), ("quantizer", C.c_float)]
+
+
+class MotionSpecParams(C.Structure):
+    """dspfft_motion_spec_params (include/dspfft.h)"""
+    _fields_ = [("mode", C.c_int), ("scalefactor", C.c_double), ("normalization", C.c_double), ("c", C.c_double)]
 
 
 _lib = None
@@ -123,6 +130,10 @@ def bind(lib):
         lib.dspfft_roundtrip_topn_work_bytes.argtypes = [vp, vp]
         lib.dspfft_execute_roundtrip_topn.argtypes = [vp, vp, vp, vp, C.POINTER(MotionFilterParams), C.c_size_t, vp, C.c_size_t, vp, vp]
         lib.dspfft_execute_roundtrip_u8_topn.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.c_size_t, vp, C.c_size_t, vp, vp]
+    if hasattr(lib, "dspfft_execute_spectrogram_u8"):     # (likewise)
+        spp, fpp = C.POINTER(MotionSpecParams), C.POINTER(MotionFilterParams)
+        lib.dspfft_execute_spectrogram_u8.argtypes = lib.dspfft_execute_spectrogram_f32.argtypes = [vp, vp, vp, vp, spp, fpp, vp, vp]
+        lib.dspfft_execute_ispectrogram_u8.argtypes = lib.dspfft_execute_ispectrogram_f32.argtypes = [vp, vp, vp, vp, spp, fpp, C.c_double, vp, vp]
     lib.dspfft_plan_set_scale_f64.argtypes = [vp, C.c_double]
     lib.dspfft_plan_set_axis_scale0_f64.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     lib.dspfft_execute_f64.argtypes = [vp, vp, vp, vp]
@@ -219,6 +230,9 @@ def bind(lib):
         lib.dspfft_motion_store_u8.argtypes = [vp, vp, ip, ip, C.c_int, C.c_double, C.c_double, C.c_double, vp]
         lib.dspfft_motion_load_f32.argtypes = [vp, vp, ip, ip, C.c_int, C.c_double, C.c_double, vp]
         lib.dspfft_motion_store_f32.argtypes = [vp, vp, ip, ip, C.c_int, C.c_double, C.c_double, C.c_double, vp]
+        if hasattr(lib, "dspfft_motion_spec_blocks_u8"):
+            for f in ("dspfft_motion_spec_blocks_u8", "dspfft_motion_spec_blocks_f32", "dspfft_motion_ispec_blocks_u8", "dspfft_motion_ispec_blocks_f32"):
+                getattr(lib, f).argtypes = [vp, vp, ip, ip, C.c_size_t, C.c_longlong, C.POINTER(MotionSpecParams), C.POINTER(MotionFilterParams), vp, vp]
         lib.dspfft_motion_topn_work_bytes.restype = C.c_size_t
         lib.dspfft_motion_topn_work_bytes.argtypes = [C.c_size_t]
         lib.dspfft_motion_topn.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]

@@ -30,6 +30,7 @@
 #include "topn_core.h"
 #include "block_rt.h"
 #include "block_rs_core.h"
+#include "block_spec_core.h"
 #include "trc_u8_core.h"
 
 using namespace dspfft;
@@ -65,6 +66,11 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_trc_lau
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_trc_launch(const dspfft::BlockRtTrcArgs *a, int nwg, size_t lds, void *stream);
 // block_rescale.hip's launcher behind a roundtrip over a rescaled block grid (motion -b with -s).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_launch(const dspfft::BlockRsArgs *a, int nwg, size_t lds, void *stream);
+// block_spec.hip's and motion_ops.hip's launchers behind dspfft_execute_spectrogram_* / _ispectrogram_*.  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_spec_launch(const dspfft::BlockSpecArgs *a, int inverse, int nwg, size_t lds, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_blocks_launch(int inverse, int u8, void *d_pix, void *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks,
+                                                                                      long long block_stride, const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter,
+                                                                                      unsigned long long *d_coeffs_coded, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_row_u8_trc_launch(int row_spec_id, const dspfft::PassArgs *a, const dspfft::U8IOTrc *io, int nwg, void *stream);
 
 static thread_local char g_err[512] = "";
@@ -1753,15 +1759,7 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 // DSPFFT_NO_FUSED_ROUNDTRIP=1: no fused column kernel and no slices.  Read on every call (tests toggle it inside one process).
 bool fused_roundtrip_off() { const char *e = getenv("DSPFFT_NO_FUSED_ROUNDTRIP"); return e && *e == '1'; }
 
-void motion_filter_of(const dspfft_motion_filter_params &fp, MotionFilter &mf)
-{
-	mf.ad = fp.active[0]; mf.ah = fp.active[1]; mf.aw = fp.active[2]; mf.mh = fp.minbuf_hw[0]; mf.mw = fp.minbuf_hw[1];
-	mf.b0d = fp.band_begin[0]; mf.b0h = fp.band_begin[1]; mf.b0w = fp.band_begin[2];
-	mf.b1d = fp.band_end[0]; mf.b1h = fp.band_end[1]; mf.b1w = fp.band_end[2];
-	mf.damp = fp.damp; mf.boost = fp.boost; mf.thr_lo = fp.threshold_lo; mf.thr_hi = fp.threshold_hi;
-	mf.preserve_dc = fp.preserve_dc; mf.grey_add = fp.grey_add; mf.quantizer = fp.quantizer; mf.enabled = 1;
-	motion_filter_set_divs(mf, fp.block_depth);
-}
+void motion_filter_of(const dspfft_motion_filter_params &fp, MotionFilter &mf) { motion_filter_from(fp, mf); }
 
 // The blocks of a plan pair as motion.c:652-668 sees them: `nblocks` runs of `count` floats (a block's whole embedding, :657), `stride` apart
 // in the working buffer.  False when the blocks are no such runs (interleaved batches, blocks lying side by side in a volume).
@@ -2295,6 +2293,146 @@ extern "C" int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, con
 {
 	if (!d_in || !d_out) return fail(-1, "null plan or buffer");         // (d_work: rt_check; a rescaled block grid needs none)
 	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream);
+}
+
+// ---- motion --spectrogram / --ispectrogram: the halves of the roundtrip, one plan each (include/dspfft.h) ----
+namespace {
+struct SpecCall {
+	dspfft_plan pl; bool inverse, u8;
+	const void *d_in; void *d_out; float *d_work;
+	const dspfft_motion_spec_params *sp; const dspfft_motion_filter_params *fp; double out_mul;
+	unsigned long long *coded; void *stream;
+};
+
+// small blocks: one kernel (block_spec.hip).  Float pixels: the end that is not next to the encode / decode is a factor of the transform
+// and rides on the plan's global scale (sample * 255 on the way in, motion.c:623; value * out_mul / 255 on the way out, :759-774).
+int spec_block(const SpecCall &c, const MotionFilter &mf)
+{
+	const dspfft_plan pl = c.pl;
+	const char *const what = c.inverse ? "ispectrogram" : "spectrogram";
+	if (!dspfft_block_spec_launch) return fail(-3, "%s over small blocks: not built into this library (the kernels are HIP-only, block_spec.hip)", what);
+	const unsigned mask = c.u8 ? 3u : 15u;
+	if ((mask & (uintptr_t)c.d_in) || (mask & (uintptr_t)c.d_out)) return fail(-2, "%s over small blocks: float buffers must be 16-byte aligned, 8-bit buffers 4-byte aligned", what);
+	BlockSpecArgs a;
+	memset((void *)&a, 0, sizeof a);
+	static_cast<BlockGeom &>(a) = pl->blk;
+	if (c.u8) { a.in8 = (const uint8_t *)c.d_in; a.out8 = (uint8_t *)c.d_out; } else { a.in = (const float *)c.d_in; a.out = (float *)c.d_out; }
+	block_scales(pl, a.s);
+	if (!c.u8) a.s.scale = c.inverse ? (float)(pl->scale * c.out_mul / 255.0) : (float)(pl->scale * 255.0);
+	a.filt = mf; a.coded = c.coded; a.mul8 = c.out_mul;
+	a.sp = MotionSpec{c.sp->mode, c.sp->scalefactor, c.sp->normalization, c.sp->c};
+	if (int rc = dspfft_block_spec_launch(&a, c.inverse, pl->blk_nwg, pl->blk_lds, c.stream)) return fail(-4, "kernel launch failed (%s over small blocks): backend code %d", what, rc);
+	return 0;
+}
+
+// every other plan: the plan's passes in d_work and motion_ops.hip's kernel over all blocks of the batch at the encoded end
+int spec_passes(const SpecCall &c)
+{
+	const dspfft_plan pl = c.pl;
+	const char *const what = c.inverse ? "ispectrogram" : "spectrogram";
+	if (!c.d_work) return fail(-1, "%s: this plan needs the float work buffer", what);
+	if (!dspfft_spec_blocks_launch) return fail(-3, "%s: not built into this library (the kernels are HIP-only, motion_ops.hip)", what);
+	const int r = pl->rank;
+	const char *const layout = "the plan must be in place on one planar layout: input strides = output strides, x contiguous, the planes of a block one pitch apart, at most one batch level";
+	for (int a = 0; a < r; a++) if (pl->axes[a].is != pl->axes[a].os) return fail(-2, "%s: %s", what, layout);
+	if (pl->axes[r - 1].os != 1) return fail(-2, "%s: %s", what, layout);
+	int n3[3] = {1, 1, pl->n[r - 1]}, hw[2] = {1, pl->n[r - 1]};
+	if (r >= 2) { n3[1] = pl->n[r - 2]; hw[0] = n3[1]; hw[1] = (int)pl->axes[r - 2].os; if (pl->axes[r - 2].os < n3[2] || pl->axes[r - 2].os > 0x7fffffffLL) return fail(-2, "%s: %s", what, layout); }
+	if (r == 3) {
+		n3[0] = pl->n[0];
+		const long long plane = pl->axes[0].os;
+		if (plane % hw[1] || plane / hw[1] < n3[1] || plane / hw[1] > 0x7fffffffLL) return fail(-2, "%s: %s", what, layout);
+		hw[0] = (int)(plane / hw[1]);
+	}
+	long long span = 1, dense = 1;
+	for (int a = 0; a < r; a++) { span += (long long)(pl->n[a] - 1) * pl->axes[a].os; dense *= pl->n[a]; }
+	std::vector<Dim> dims;
+	for (const Dim &b : pl->batches) if (b.n > 1) { if (b.is != b.os) return fail(-2, "%s: %s", what, layout); dims.push_back(b); }
+	merge_dims(dims);
+	if (dims.size() > 1 || (dims.size() == 1 && dims[0].os < span)) return fail(-2, "%s: %s", what, layout);
+	const size_t nblocks = dims.empty() ? 1 : (size_t)dims[0].n;
+	const long long stride = dims.empty() ? span : dims[0].os;
+	dense *= (long long)nblocks;
+	span += (long long)(nblocks - 1) * stride;
+	const size_t np = pl->passes.size();
+	// the 8-bit end on the transform's side: the first (last) pass where it is a planar row pass with an 8-bit kernel, else one sweep
+	const bool fused8 = c.u8 && np >= 2 && pass_has_u8(pl, pl->passes[c.inverse ? np - 1 : 0]);
+	if (c.u8 && c.inverse && !fused8 && dense != span) return fail(-2, "%s: 8-bit output without a planar specialised row pass needs a dense layout", what);
+	float *const w = c.d_work;
+	const dspfft_motion_spec_params plain_in = {DSPFFT_MOTION_NONE, 1.0, 1.0, 0.0}, plain_out = {DSPFFT_MOTION_NONE, c.out_mul, 1.0, 0.0};
+	auto blocks = [&](int inverse, void *pix, const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *fp, unsigned long long *coded) {
+		if (dspfft_spec_blocks_launch(inverse, c.u8, pix, w, n3, hw, nblocks, stride, sp, fp, coded, c.stream))
+			return fail(-4, "%s: %s", what, dspfft_motion_last_error ? dspfft_motion_last_error() : "launch failed");
+		return 0;
+	};
+	if (!c.inverse) {
+		if (c.u8 && !fused8 && be_u8_to_f32(w, (const uint8_t *)c.d_in, (uint64_t)span, c.stream)) return fail(-4, "launch failed");
+		if (!c.u8) if (int rc = blocks(1, (void *)c.d_in, &plain_in, nullptr, nullptr)) return rc;            // sample * 255 (motion.c:623)
+		for (size_t i = 0; i < np; i++) {
+			const Pass &P = pl->passes[i];
+			if (i == 0 && fused8) {
+				U8IO io; io.in = (const uint8_t *)c.d_in; io.out = nullptr; io.mul = 1.0;
+				if (int rc = run_pass_u8(pl, P, w, w, false, io, c.stream)) return rc;
+			} else if (int rc = run_pass<float>(pl, P, (const float *)w, w, i + 1 == np, c.stream)) return rc;
+		}
+		return blocks(0, c.d_out, c.sp, c.fp, c.coded);
+	}
+	if (int rc = blocks(1, (void *)c.d_in, c.sp, c.fp, c.coded)) return rc;
+	for (size_t i = 0; i < np; i++) {
+		const Pass &P = pl->passes[i];
+		if (i + 1 == np && fused8) {
+			U8IO io; io.in = nullptr; io.out = (uint8_t *)c.d_out; io.mul = c.out_mul;
+			if (int rc = run_pass_u8(pl, P, w, w, true, io, c.stream)) return rc;
+		} else if (int rc = run_pass<float>(pl, P, (const float *)w, w, i + 1 == np, c.stream)) return rc;
+	}
+	if (c.u8) return !fused8 && be_f32_to_u8((uint8_t *)c.d_out, w, c.out_mul, (uint64_t)span, c.stream) ? fail(-4, "launch failed") : 0;
+	return blocks(0, c.d_out, &plain_out, nullptr, nullptr);                                                  // value * out_mul / 255 (:759-774)
+}
+
+// every rejection of this function, of spec_block and of spec_passes comes before the first launch (what the kernels' own launchers refuse
+// beyond that -- a block of 2^32 samples -- surfaces from spec_passes after its earlier sweeps have written d_work)
+int spec_core(const SpecCall &c)
+{
+	const dspfft_plan pl = c.pl;
+	const char *const what = c.inverse ? "ispectrogram" : "spectrogram";
+	if (!pl || !c.d_in || !c.d_out || !c.sp) return fail(-1, "null plan or buffer");
+	if (pl->f64) return fail(-2, "%s: f64 plans are not implemented", what);
+	if (pl->u8_trc) return fail(-2, "%s: a plan with a transfer characteristic (dspfft_plan_set_u8_trc) is not implemented", what);
+	const int m = c.sp->mode;
+	if (c.inverse && m == DSPFFT_MOTION_ABS) return fail(-2, "ispectrogram: the reference has no abs type (motion.c:627-630): shift, flat or copy");
+	if (m != DSPFFT_MOTION_ABS && m != DSPFFT_MOTION_SHIFT && m != DSPFFT_MOTION_FLAT && m != DSPFFT_MOTION_COPY) return fail(-1, "%s: mode must be %sshift, flat or copy", what, c.inverse ? "" : "abs, ");
+	for (int a = 0; a < pl->rank; a++)
+		if (pl->kinds[a] != (c.inverse ? DSPFFT_REDFT01 : DSPFFT_REDFT10)) return fail(-1, "%s: the plan must be %s on every axis", what, c.inverse ? "REDFT01" : "REDFT10");
+	MotionFilter mf;
+	memset((void *)&mf, 0, sizeof mf);
+	if (c.fp) {
+		if (c.fp->preserve_dc < 0 || c.fp->preserve_dc > 2 || c.fp->minbuf_hw[0] < 1 || c.fp->minbuf_hw[1] < 1 || c.fp->block_depth < 1) return fail(-1, "bad filter parameters");
+		motion_filter_of(*c.fp, mf);
+	}
+	if (pl->has_block) return spec_block(c, mf);
+	return spec_passes(c);
+}
+}  // namespace
+
+extern "C" int dspfft_execute_spectrogram_u8(dspfft_plan fwd, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                             const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_core(SpecCall{fwd, false, true, d_in, d_out, d_work, sp, fp, 1.0, d_coeffs_coded, stream});
+}
+extern "C" int dspfft_execute_spectrogram_f32(dspfft_plan fwd, const float *d_in, float *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                              const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_core(SpecCall{fwd, false, false, d_in, d_out, d_work, sp, fp, 1.0, d_coeffs_coded, stream});
+}
+extern "C" int dspfft_execute_ispectrogram_u8(dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                              const dspfft_motion_filter_params *fp, double out_mul, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_core(SpecCall{inv, true, true, d_in, d_out, d_work, sp, fp, out_mul, d_coeffs_coded, stream});
+}
+extern "C" int dspfft_execute_ispectrogram_f32(dspfft_plan inv, const float *d_in, float *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                               const dspfft_motion_filter_params *fp, double out_mul, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_core(SpecCall{inv, true, false, d_in, d_out, d_work, sp, fp, out_mul, d_coeffs_coded, stream});
 }
 
 extern "C" size_t dspfft_roundtrip_topn_work_bytes(dspfft_plan fwd, dspfft_plan inv)

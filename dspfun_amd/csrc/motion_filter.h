@@ -143,5 +143,75 @@ DSP_HD double motion_store_pel(double c, int mode, double scalefactor, double no
 	default: return pel * norm;
 	}
 }
+// motion.c:776: the 8-bit store of a pel (a NaN pel -- abs over a block whose DC is 0, :755 -- gives an unspecified byte)
+DSP_HD uint32_t motion_pel_u8(double pel) { return pel > 255 ? 255u : pel < 0 ? 0u : (uint32_t)lround(pel); }
+// motion.c:755: --spectrogram=abs takes its constant from the block's own DC as it was before the filter (:650)
+DSP_HD double motion_abs_c(float dc, double scalefactor, double norm) { return 255 / log1p(fabs((double)dc * scalefactor * norm)); }
+
+// ---- the 8-bit abs / shift encode in single precision, where that decides the byte ----
+// motion_store_pel's double log1p is some 350 instructions a sample and made the fused spectrogram kernels issue-bound (profiles/r11_motion_spec.txt).
+// r' = cc' log1pf(|v m'|) (+ 127.5 with the sign) with m' = RN(scalefactor normalization), cc' = RN(cc), u = 2^-24:
+//   p' = v m' is within 2u of the double line's pel relatively (u for m', u for the product); log1p moves an argument's relative error by
+//   x / ((1 + x) log1p x) <= 1, and log1pf adds at most 4 ulp = 8u (the device library and glibc state 1 or 2); cc' and the product add 2u:
+//   |t' - t| <= 13u |t|.  Inside the window -1 < r' < 257 |t| < 258.5, so that is below 2.01e-4; shift's float addition rounds by at most half
+//   an ulp of [256, 512), 2^-16 = 1.6e-5, and the fraction below is exact but for 2^-24: |r' - r| < 2.2e-4 < B = 2^-12.
+// So when r' is farther than B from every half-integer, r lies between the same two and rounds to the same integer (away from the halves
+// lround is floor(r + 1/2) for either sign), and :776's clamps act on that integer alike: n <= 0 gives 0 whether r < 0 or lround(r) = 0, n >= 255
+// gives 255.  Outside the window r' >= 257 means r > 255 and r' <= -1 means r < 0 (the relative bound holds for every finite p').  Everything
+// else -- within B of a half-integer (a share 2B = 0.05 % of samples), p' not finite (v m' overflows where the double product does not), NaN --
+// returns false and the caller evaluates the double line.  motion_fast_of switches the path off for constants whose float images are not
+// normal numbers with full precision.  The byte EQUALS the double line's for every float coefficient: tests/test_motion_spec_cpu.py on the
+// host's libm, tests/test_motion_spec_gpu.py on the device's.
+struct MotionFast { float m, cc; int on; };
+DSP_HD MotionFast motion_fast_of(int mode, double scalefactor, double norm, double cc)
+{
+	const double m = scalefactor * norm;
+	MotionFast f;
+	f.m = (float)m; f.cc = (float)cc;
+	f.on = (mode == MOTION_MODE_ABS || mode == MOTION_MODE_SHIFT) && fabs(m) > 1e-30 && fabs(m) < 1e30 && fabs(cc) > 1e-30 && fabs(cc) < 1e30;
+	return f;
+}
+DSP_HD bool motion_store_u8_fast(float v, int mode, const MotionFast &f, uint32_t &byte)
+{
+	const float p = v * f.m;
+	if (!(fabsf(p) <= 3e38f)) return false;
+	const float t = f.cc * log1pf(fabsf(p));
+	const float r = mode == MOTION_MODE_ABS ? t : copysignf(t, p) + 127.5f;
+	// shift's zero and small non-negative coefficients (what a quantiser leaves of most): r' sits on the half-integer 127.5 itself, but the
+	// sign says on which side r lies: 127.5 <= r < 128.01, and lround takes 127.5 up (a zero of either sign is 127.5 in the double line too; a
+	// negative product that underflowed to -0 is not)
+	if (mode == MOTION_MODE_SHIFT && (v == 0.f || !__builtin_signbitf(p)) && t >= 0.f && t <= 0.5f) { byte = 128u; return true; }
+	if (r >= 257.f) { byte = 255u; return true; }
+	if (r <= -1.f) { byte = 0u; return true; }
+	if (!(r > -1.f)) return false;                                              // NaN
+	const float fl = floorf(r), frac = r - fl;
+	if (fabsf(frac - 0.5f) <= 0x1p-12f) return false;
+	const float n = frac > 0.5f ? fl + 1.f : fl;
+	byte = n <= 0.f ? 0u : n >= 255.f ? 255u : (uint32_t)n;
+	return true;
+}
+// the byte of one coefficient (motion.c:759-776): the fast line where it decides, else the double line
+DSP_HD uint32_t motion_spec_byte(float v, int mode, double scalefactor, double norm, double cc, const MotionFast &f)
+{
+	uint32_t b;
+	if (f.on && motion_store_u8_fast(v, mode, f, b)) return b;
+	return motion_pel_u8(motion_store_pel((double)v, mode, scalefactor, norm, cc));
+}
+
+// one spectrogram call's encode or decode (dspfft_motion_spec_params): c is :568's (spectrogram, shift) or :569's (ispectrogram, shift); abs derives
+// its own per block (motion_abs_c)
+struct MotionSpec { int mode; double scalefactor, norm, c; };
+
+// dspfft_motion_filter_params (include/dspfft.h) as the kernels take it
+template <class P>
+inline void motion_filter_from(const P &fp, MotionFilter &mf)
+{
+	mf.ad = fp.active[0]; mf.ah = fp.active[1]; mf.aw = fp.active[2]; mf.mh = fp.minbuf_hw[0]; mf.mw = fp.minbuf_hw[1];
+	mf.b0d = fp.band_begin[0]; mf.b0h = fp.band_begin[1]; mf.b0w = fp.band_begin[2];
+	mf.b1d = fp.band_end[0]; mf.b1h = fp.band_end[1]; mf.b1w = fp.band_end[2];
+	mf.damp = fp.damp; mf.boost = fp.boost; mf.thr_lo = fp.threshold_lo; mf.thr_hi = fp.threshold_hi;
+	mf.preserve_dc = fp.preserve_dc; mf.grey_add = fp.grey_add; mf.quantizer = fp.quantizer; mf.enabled = 1;
+	motion_filter_set_divs(mf, fp.block_depth);
+}
 
 }  // namespace dspfft

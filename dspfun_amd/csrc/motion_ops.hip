@@ -58,6 +58,87 @@ __global__ void motion_store_kernel(PIX *pix, const float *c, Reg r, int mode, d
 	}
 }
 
+// ---- motion --spectrogram / --ispectrogram over all blocks of a batch (dspfft_motion_spec_blocks_*, dspfft_motion_ispec_blocks_*) ----
+// Block b (blockIdx.y, striding) lies at b * stride; its element (z, y, x) at (z mh + y) mw + x, in the pixel and the coefficient buffer alike.
+// A thread moves W = 4 consecutive samples of a row where rows and pitches are multiples of 4 and the buffers aligned, else one.
+struct SpecReg { int n[3]; long long mh, mw, stride; unsigned int nblocks; };
+__device__ inline void coded_add(unsigned long long mine, unsigned long long *coded)
+{
+	unsigned int m = (unsigned int)mine;
+	for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
+	if ((threadIdx.x & 63) == 0 && m) atomicAdd(coded, (unsigned long long)m);
+}
+// motion.c:650,683-744,755-776: c is read only -- the block's element 0 is still its DC from before the filter when abs asks for it (:755)
+template <class PIX, int W>
+__global__ void __launch_bounds__(256) motion_spec_blocks_kernel(PIX *pix, const float *c, SpecReg r, dspfft::MotionSpec sp, dspfft::MotionFilter f, unsigned long long *coded)
+{
+	const uint32_t qx = (uint32_t)r.n[2] / W, per = (uint32_t)r.n[0] * r.n[1] * qx;
+	unsigned long long mine = 0;
+	for (uint32_t b = blockIdx.y; b < r.nblocks; b += gridDim.y) {
+		const float *cb = c + (long long)b * r.stride;
+		PIX *pb = pix + (long long)b * r.stride;
+		const double cc = sp.mode == dspfft::MOTION_MODE_ABS ? dspfft::motion_abs_c(cb[0], sp.scalefactor, sp.norm) : sp.c;
+		const dspfft::MotionFast fast = dspfft::motion_fast_of(sp.mode, sp.scalefactor, sp.norm, cc);
+		for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < per; e += gridDim.x * blockDim.x) {
+			const uint32_t row = e / qx, x = (e - row * qx) * W, z = row / (uint32_t)r.n[1], y = row - z * (uint32_t)r.n[1];
+			const long long o = ((long long)z * r.mh + y) * r.mw + x;
+			float v[W];
+			if constexpr (W == 4) { const float4 t = *reinterpret_cast<const float4 *>(cb + o); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+			else v[0] = cb[o];
+#pragma unroll
+			for (int k = 0; k < W; k++)
+				if (f.enabled && (int)(x + k) < f.aw && (int)y < f.ah && (int)z < f.ad) v[k] = dspfft::motion_filter_at(f, (int)z, (int)y, (int)(x + k), v[k], mine);
+			if constexpr (sizeof(PIX) == 1) {                                                                       // :759-776
+				uint32_t w4 = 0;
+#pragma unroll
+				for (int k = 0; k < W; k++) w4 |= dspfft::motion_spec_byte(v[k], sp.mode, sp.scalefactor, sp.norm, cc, fast) << (8 * k);
+				if constexpr (W == 4) *reinterpret_cast<uint32_t *>(pb + o) = w4; else pb[o] = (uint8_t)w4;
+			} else {                                                                                                // :774
+				double pel[W];
+#pragma unroll
+				for (int k = 0; k < W; k++) pel[k] = dspfft::motion_store_pel((double)v[k], sp.mode, sp.scalefactor, sp.norm, cc);
+				if constexpr (W == 4) {
+					float4 t; t.x = (float)(pel[0] / 255); t.y = (float)(pel[1] / 255); t.z = (float)(pel[2] / 255); t.w = (float)(pel[3] / 255);
+					*reinterpret_cast<float4 *>(pb + o) = t;
+				} else pb[o] = (float)(pel[0] / 255);
+			}
+		}
+	}
+	if (coded && f.enabled) coded_add(mine, coded);
+}
+// motion.c:621-637,650,683-744: pixel -> the coefficient it stands for -> filtered (the DC the filter keeps is the decoded one, :650)
+template <class PIX, int W>
+__global__ void __launch_bounds__(256) motion_ispec_blocks_kernel(float *c, const PIX *pix, SpecReg r, dspfft::MotionSpec sp, dspfft::MotionFilter f, unsigned long long *coded)
+{
+	const uint32_t qx = (uint32_t)r.n[2] / W, per = (uint32_t)r.n[0] * r.n[1] * qx;
+	unsigned long long mine = 0;
+	for (uint32_t b = blockIdx.y; b < r.nblocks; b += gridDim.y) {
+		float *cb = c + (long long)b * r.stride;
+		const PIX *pb = pix + (long long)b * r.stride;
+		for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < per; e += gridDim.x * blockDim.x) {
+			const uint32_t row = e / qx, x = (e - row * qx) * W, z = row / (uint32_t)r.n[1], y = row - z * (uint32_t)r.n[1];
+			const long long o = ((long long)z * r.mh + y) * r.mw + x;
+			double pel[W];
+			if constexpr (sizeof(PIX) == 1) {
+				if constexpr (W == 4) { const uint32_t w4 = *reinterpret_cast<const uint32_t *>(pb + o); for (int k = 0; k < 4; k++) pel[k] = (double)((w4 >> (8 * k)) & 0xffu); }
+				else pel[0] = (double)pb[o];
+			} else {                                                                                                // :623 float * int: a float product
+				if constexpr (W == 4) { const float4 t = *reinterpret_cast<const float4 *>(pb + o); pel[0] = (double)(t.x * 255.0f); pel[1] = (double)(t.y * 255.0f); pel[2] = (double)(t.z * 255.0f); pel[3] = (double)(t.w * 255.0f); }
+				else pel[0] = (double)(pb[o] * 255.0f);
+			}
+			float v[W];
+#pragma unroll
+			for (int k = 0; k < W; k++) {
+				v[k] = (float)dspfft::motion_load_pel(pel[k], sp.mode, sp.c, sp.norm);                                  // :627-637
+				if (f.enabled && (int)(x + k) < f.aw && (int)y < f.ah && (int)z < f.ad) v[k] = dspfft::motion_filter_at(f, (int)z, (int)y, (int)(x + k), v[k], mine);
+			}
+			if constexpr (W == 4) { float4 t; t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3]; *reinterpret_cast<float4 *>(cb + o) = t; }
+			else cb[o] = v[0];
+		}
+	}
+	if (coded && f.enabled) coded_add(mine, coded);
+}
+
 // motion --linear with float pixels (--ispec / --spec none; copy stores alike).  The reference feeds the function a double, keeps the double
 // it returns and divides by 255 outside it, so these two use trc_core.h's exact evaluation (double, the device library's pow) and not the
 // production one, whose 1-ulp statement is about a float argument and a float result.
@@ -303,6 +384,67 @@ extern "C" int dspfft_motion_store_f32(float *d_pix, const float *d_coeffs, cons
 	Reg r; r.n[0] = n[0]; r.n[1] = n[1]; r.n[2] = n[2]; r.mh = minbuf_hw[0]; r.mw = minbuf_hw[1];
 	hipLaunchKernelGGL(motion_store_kernel<float>, dim3(mgrid((size_t)n[0] * n[1] * n[2])), dim3(256), 0, (hipStream_t)stream, d_pix, d_coeffs, r, spec_mode, scalefactor, normalization, c);
 	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+namespace {
+template <class PIX, int W>
+void spec_blocks_launch(bool inverse, void *pix, void *c, const SpecReg &r, const dspfft::MotionSpec &sp, const dspfft::MotionFilter &f, unsigned long long *coded, hipStream_t s)
+{
+	const size_t per = (size_t)r.n[0] * r.n[1] * (r.n[2] / W);
+	const dim3 grid((unsigned)std::min<size_t>((per + 255) / 256, 4096), std::min(r.nblocks, 65535u));
+	if (inverse) hipLaunchKernelGGL((motion_ispec_blocks_kernel<PIX, W>), grid, dim3(256), 0, s, (float *)c, (const PIX *)pix, r, sp, f, coded);
+	else hipLaunchKernelGGL((motion_spec_blocks_kernel<PIX, W>), grid, dim3(256), 0, s, (PIX *)pix, (const float *)c, r, sp, f, coded);
+}
+int spec_blocks_call(bool inverse, bool u8, void *d_pix, void *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                     const dspfft_motion_spec_params *spp, const dspfft_motion_filter_params *fp, unsigned long long *d_coded, void *stream)
+{
+	if (!d_coeffs || !d_pix || !n || !minbuf_hw || !spp || !nblocks || n[0] < 1 || n[1] < 1 || n[2] < 1 || minbuf_hw[0] < n[1] || minbuf_hw[1] < n[2]) return mbad("bad arguments");
+	const int m = spp->mode;
+	if (m < DSPFFT_MOTION_NONE || m > DSPFFT_MOTION_COPY || (inverse && m == DSPFFT_MOTION_ABS)) return mbad(inverse ? "ispec mode: none, shift, flat or copy" : "spec mode: none, abs, shift, flat or copy");
+	if ((unsigned long long)n[0] * n[1] * n[2] >= (1ull << 32) || nblocks >= (1ull << 32)) return mbad("a block of 2^32 samples or more, or 2^32 blocks or more");
+	SpecReg r; r.n[0] = n[0]; r.n[1] = n[1]; r.n[2] = n[2]; r.mh = minbuf_hw[0]; r.mw = minbuf_hw[1]; r.stride = nblocks > 1 ? block_stride : 0; r.nblocks = (unsigned int)nblocks;
+	if (nblocks > 1 && block_stride < ((long long)(n[0] - 1) * r.mh + n[1] - 1) * r.mw + n[2]) return mbad("the blocks overlap (block_stride < a block's span)");
+	if (fp && (fp->preserve_dc < 0 || fp->preserve_dc > 2 || fp->minbuf_hw[0] < 1 || fp->minbuf_hw[1] < 1 || fp->block_depth < 1)) return mbad("bad filter parameters");
+	dspfft::MotionFilter f;
+	memset((void *)&f, 0, sizeof f);
+	if (fp) dspfft::motion_filter_from(*fp, f);
+	const dspfft::MotionSpec sp = {m, spp->scalefactor, spp->normalization, spp->c};
+	const bool vec = n[2] % 4 == 0 && r.mw % 4 == 0 && r.stride % 4 == 0 && !((uintptr_t)d_pix & (u8 ? 3u : 15u)) && !((uintptr_t)d_coeffs & 15u);
+	hipStream_t s = (hipStream_t)stream;
+	if (u8) { if (vec) spec_blocks_launch<uint8_t, 4>(inverse, d_pix, d_coeffs, r, sp, f, d_coded, s); else spec_blocks_launch<uint8_t, 1>(inverse, d_pix, d_coeffs, r, sp, f, d_coded, s); }
+	else { if (vec) spec_blocks_launch<float, 4>(inverse, d_pix, d_coeffs, r, sp, f, d_coded, s); else spec_blocks_launch<float, 1>(inverse, d_pix, d_coeffs, r, sp, f, d_coded, s); }
+	return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+}  // namespace
+
+extern "C" int dspfft_motion_spec_blocks_u8(uint8_t *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                            const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_blocks_call(false, true, d_pix, (void *)d_coeffs, n, minbuf_hw, nblocks, block_stride, sp, filter, d_coeffs_coded, stream);
+}
+extern "C" int dspfft_motion_spec_blocks_f32(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                             const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_blocks_call(false, false, d_pix, (void *)d_coeffs, n, minbuf_hw, nblocks, block_stride, sp, filter, d_coeffs_coded, stream);
+}
+extern "C" int dspfft_motion_ispec_blocks_u8(float *d_coeffs, const uint8_t *d_pix, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                             const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_blocks_call(true, true, (void *)d_pix, d_coeffs, n, minbuf_hw, nblocks, block_stride, sp, filter, d_coeffs_coded, stream);
+}
+extern "C" int dspfft_motion_ispec_blocks_f32(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                              const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_blocks_call(true, false, (void *)d_pix, d_coeffs, n, minbuf_hw, nblocks, block_stride, sp, filter, d_coeffs_coded, stream);
+}
+
+/* the same for dspfft_execute_spectrogram_* / _ispectrogram_* (engine.cpp reaches this through a weak reference); the error text is
+ * dspfft_motion_last_error's */
+extern "C" __attribute__((visibility("hidden"))) int dspfft_spec_blocks_launch(int inverse, int u8, void *d_pix, void *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks,
+                                                                                long long block_stride, const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter,
+                                                                                unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_blocks_call(inverse != 0, u8 != 0, d_pix, d_coeffs, n, minbuf_hw, nblocks, block_stride, sp, filter, d_coeffs_coded, stream);
 }
 
 /* dspfft_motion_{load,store}_f32_linear's body (engine.cpp has checked the arguments and reaches this through a weak reference) */

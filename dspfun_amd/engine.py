@@ -230,6 +230,28 @@ class Plan:
                                                                  float(scalefactor), float(normalization), C.byref(fp) if fp is not None else None,
                                                                  C.c_void_p(d_coded or None), C.c_void_p(stream)))
 
+    def spectrogram(self, d_in, d_out, mode, scalefactor, normalization, c=None, d_work=0, filter=None, d_coded=0, stream=0, pixels="u8"):
+        """motion --spectrogram (dspfft_execute_spectrogram_u8 / _f32): load -> self (REDFT10 with motion's index-0 factors) -> filter ->
+        encode -> store, one kernel for a small-block plan, the plan's passes and one kernel over all blocks otherwise (d_work needed).
+        mode: "abs", "shift", "flat" or "copy" (or DSPFFT_MOTION_*).  c: shift's constant (motion.c:568; motion_spec_constants gives it),
+        None for the other modes -- abs derives its own per block on the device.  pixels: "u8", or "f32" for motion's float pixels."""
+        sp = _spec_params(mode, scalefactor, normalization, c)
+        fp = self._filter_params(filter)
+        run = {"u8": self._lib.dspfft_execute_spectrogram_u8, "f32": self._lib.dspfft_execute_spectrogram_f32}[pixels]
+        self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), C.byref(fp) if fp is not None else None,
+                        C.c_void_p(d_coded or None), C.c_void_p(stream)))
+
+    def ispectrogram(self, d_in, d_out, mode, scalefactor, normalization, c=None, d_work=0, filter=None, d_coded=0, stream=0, pixels="u8", out_mul=None):
+        """motion --ispectrogram (dspfft_execute_ispectrogram_u8 / _f32): load -> decode -> filter -> self (REDFT01 with motion.c:751's
+        factors and the global scale) -> store.  mode: "shift", "flat" or "copy"; c: shift's ic (motion.c:569).  out_mul: roundtrip_u8's,
+        scalefactor normalization^2 by default."""
+        sp = _spec_params(mode, scalefactor, normalization, c)
+        fp = self._filter_params(filter)
+        mul = float(scalefactor) * float(normalization) ** 2 if out_mul is None else float(out_mul)
+        run = {"u8": self._lib.dspfft_execute_ispectrogram_u8, "f32": self._lib.dspfft_execute_ispectrogram_f32}[pixels]
+        self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), C.byref(fp) if fp is not None else None,
+                        mul, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+
     def describe(self):
         buf = C.create_string_buffer(4096)
         self._check(self._lib.dspfft_plan_describe(self._h, buf, len(buf)))
@@ -371,6 +393,50 @@ def trc_apply(t, trc, inverse=False, out=None, stream=None, lib=None):
 
 
 _MOTION_MODES = {"none": 0, "abs": 1, "shift": 2, "flat": 3, "copy": 4}
+
+
+def _spec_params(mode, scalefactor, normalization, c=None):
+    m = _MOTION_MODES[mode] if isinstance(mode, str) else int(mode)
+    return _lib.MotionSpecParams(m, float(scalefactor), float(normalization), 0.0 if c is None else float(c))
+
+
+def motion_spec_constants(block, scaled=None):
+    """motion.c:566-569 for blocks of `block` = (d, h, w) stored as `scaled` (default: block): scalefactor, normalization, and the shift
+    types' constants c (--spectrogram=shift) and ic (--ispectrogram=shift), which are the same number"""
+    import math
+    scaled = block if scaled is None else scaled
+    nb, ns = float(block[0] * block[1] * block[2]), float(scaled[0] * scaled[1] * scaled[2])
+    scalefactor, normalization = ns / nb, 1.0 / math.sqrt(ns * 8)
+    c = 127.5 / math.log1p(ns * normalization * 255 * 8)
+    return dict(scalefactor=scalefactor, normalization=normalization, c=c, ic=c)
+
+
+def _spec_blocks(fn, d_a, d_b, n, minbuf_hw, nblocks, block_stride, mode, scalefactor, normalization, c, filter, d_coded, stream, lib):
+    lib = lib or _lib.load()
+    n = [int(v) for v in n]
+    hw = (n[1], n[2]) if minbuf_hw is None else minbuf_hw
+    stride = hw[0] * hw[1] * n[0] if block_stride is None else int(block_stride)
+    sp = _spec_params(mode, scalefactor, normalization, c)
+    fp = Plan._filter_params(filter)
+    if getattr(lib, fn)(_ptr(d_a), _ptr(d_b), _ia(n), _ia(hw), int(nblocks), stride, C.byref(sp), C.byref(fp) if fp is not None else None,
+                        C.c_void_p(d_coded or None), C.c_void_p(stream)):
+        raise DspfftError(lib.dspfft_motion_last_error().decode())
+
+
+def motion_spec_blocks(d_pix, d_coeffs, n, mode, scalefactor, normalization, c=None, minbuf_hw=None, nblocks=1, block_stride=None, filter=None,
+                       d_coded=0, stream=0, pixels="u8", lib=None):
+    """dspfft_motion_spec_blocks_u8 / _f32: filter, encode and store the `nblocks` blocks of n = (d, h, w) coefficients in d_coeffs (read
+    only; planes of minbuf_hw, blocks block_stride apart: dense by default) as pixels in d_pix, the same layout.  abs takes every block's c
+    from its own element 0."""
+    _spec_blocks("dspfft_motion_spec_blocks_" + pixels, d_pix, d_coeffs, n, minbuf_hw, nblocks, block_stride, mode, scalefactor, normalization, c,
+                 filter, d_coded, stream, lib)
+
+
+def motion_ispec_blocks(d_coeffs, d_pix, n, mode, scalefactor, normalization, c=None, minbuf_hw=None, nblocks=1, block_stride=None, filter=None,
+                        d_coded=0, stream=0, pixels="u8", lib=None):
+    """dspfft_motion_ispec_blocks_u8 / _f32: load, decode (c is ic for shift) and filter the pixels of d_pix into coefficients in d_coeffs"""
+    _spec_blocks("dspfft_motion_ispec_blocks_" + pixels, d_coeffs, d_pix, n, minbuf_hw, nblocks, block_stride, mode, scalefactor, normalization, c,
+                 filter, d_coded, stream, lib)
 
 
 def _motion_linear(fn, mode, allowed, d_dst, d_src, n, minbuf_hw, extra, trc, stream, lib):

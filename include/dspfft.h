@@ -351,6 +351,48 @@ int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv, const uin
                                      const dspfft_motion_filter_params *filter, size_t keep, void *d_topn_work, size_t work_bytes,
                                      unsigned long long *d_coeffs_coded, void *hip_stream);
 
+/* motion --spectrogram and --ispectrogram (motion/motion.c:617-776 with `spec` / `ispec` set) as one call per clip: the two halves of
+ * the roundtrip above, each with ONE plan.
+ *   spectrogram   load (:621-625) -> REDFT10 over `fwd`'s extents (`fwd` carries motion's index-0 factors, dspfft_plan_set_axis_scale0,
+ *                 :647) -> dc = the block's element 0 (:650) -> filter (:683-744, d_coeffs_coded as above) -> encode (:755-771) -> store:
+ *                 8-bit clamp + lround (:776), float pel / 255 (:774).  mode: abs, shift, flat or copy.
+ *   ispectrogram  load (the 8-bit sample, or the float sample * 255 as a float product, :623) -> decode (:627-630) -> filter -> REDFT01
+ *                 over `inv`'s extents (`inv` carries :751's factors and the global scale) -> store as dspfft_execute_roundtrip_u8 stores:
+ *                 quantise(value * out_mul), out_mul = scalefactor normalization^2; the float form stores value * out_mul / 255.
+ *                 mode: shift, flat or copy (the reference has no abs type here: -2).
+ * The _f32 forms are motion's float_pixels (planar float formats, what the reference picks for flat and copy by default), not raw
+ * coefficients.  sp->c is :568's constant (spectrogram, shift) or :569's (ispectrogram, shift) and ignored otherwise: for abs every block's
+ * own c = 255 / log1p(|dc scalefactor normalization|) (:755) is derived on the device from that block's DC, with no host round trip.  A
+ * block whose DC is exactly 0 under abs is outside the contract (the reference computes 255 / 0 there): the call succeeds and that block's
+ * samples are unspecified.  The 8-bit abs / shift encode runs in single precision wherever that decides the byte and in double next to a
+ * rounding boundary (motion_filter.h): the byte is the double evaluation's for every coefficient.  The filter is the roundtrip's, `active` = the block; filter == NULL: none.
+ * Small-block plans (every extent 4, 8 or 16, 2-D blocks up to 32, x contiguous; the blocks of a volume via dspfft_plan_guru_r2r or a
+ * block-major stack via dspfft_plan_many_r2r -- the plans the fused block roundtrip takes): each call is ONE kernel, 2 B/sample on 8-bit
+ * pixels.  d_in is read in the plan's input layout and d_out written in its output layout, so in the volume layout every block's
+ * spectrogram lands where the block was (:795-802).  d_work is not touched and may be NULL; float buffers must be 16-byte aligned and 8-bit
+ * ones 4-byte (-2 otherwise); d_in == d_out is allowed (a workgroup has read its blocks before it writes them).
+ * Every other plan (motion's default -b 0x0x1 over a clip: a 2-D plan with a batch of frames; one 3-D block): the plan must be in place on
+ * one layout (input strides = output strides, x contiguous, planes of a block one pitch apart, at most one batch level, -2 otherwise),
+ * which d_in, d_work and d_out share element for element.  spectrogram: the forward passes -- the first with the plan's fused 8-bit row
+ * load where it has one, after dspfft_u8_to_f32 otherwise -- into d_work, then dspfft_motion_spec_blocks_* (below) once over all blocks
+ * of the batch; ispectrogram: dspfft_motion_ispec_blocks_* once into d_work, then the inverse passes, the last with the plan's fused
+ * 8-bit store where it has one (dspfft_f32_to_u8 otherwise, which needs a dense layout).  A float-pixel call converts its linear end with
+ * one more sweep of the same kernels.  d_work is required (-1).
+ * Refused with -2, the reason in dspfft_last_error and nothing launched -- each a stated follow-up: a plan with dspfft_plan_set_u8_trc set
+ * (--linear with a spectrogram), an f64 plan, abs passed to an ispectrogram call, misaligned buffers with a small-block plan.  A plan pair is
+ * not involved, so motion's `scaled != block` (-s with --spectrogram) does not arise: a caller who wants it runs the forward plan and encodes
+ * the scaled corner with dspfft_motion_spec_blocks_*.  There is no coefficient-limit and no dithered variant (the reference disables -d with
+ * --spectrogram).  -3 from a library built without the HIP kernels. */
+typedef struct { int mode; double scalefactor, normalization, c; } dspfft_motion_spec_params;   /* mode: DSPFFT_MOTION_* (below) */
+int dspfft_execute_spectrogram_u8(dspfft_plan fwd, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                  const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_execute_spectrogram_f32(dspfft_plan fwd, const float *d_in, float *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                   const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_execute_ispectrogram_u8(dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                   const dspfft_motion_filter_params *filter, double out_mul, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_execute_ispectrogram_f32(dspfft_plan inv, const float *d_in, float *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                    const dspfft_motion_filter_params *filter, double out_mul, unsigned long long *d_coeffs_coded, void *hip_stream);
+
 /* Replaces fftw(destroy_plan). */
 void dspfft_destroy_plan(dspfft_plan plan);
 
@@ -529,6 +571,22 @@ int dspfft_motion_store_u8(uint8_t *d_pix, const float *d_coeffs, const int n[3]
 int dspfft_motion_load_f32(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], int ispec_mode, double ic, double normalization, void *hip_stream);
 int dspfft_motion_store_f32(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], int spec_mode,
                             double scalefactor, double normalization, double c, void *hip_stream);
+/* The store and the load of a spectrogram over ALL blocks of a batch in one launch (what dspfft_execute_spectrogram_* and
+ * dspfft_execute_ispectrogram_* run beside the passes of a plan that is no small-block plan).  Block b of nblocks lies at b * block_stride
+ * elements and its element (z, y, x) at (z minbuf_hw[0] + y) minbuf_hw[1] + x, in d_pix and d_coeffs alike (nblocks = 1: block_stride is
+ * not consulted).  The filter acts on the block's own positions inside filter->active; filter == NULL: none.
+ *   spec_blocks   d_coeffs is READ, never written: per coefficient the filter (motion.c:683-744), then the encode with sp (:755-771; abs:
+ *                 c from the block's element 0 as d_coeffs holds it, :650,755) and the store (:774,776).  5 B/sample on 8-bit pixels.
+ *   ispec_blocks  per pixel the load (:621-625), the decode with sp (:627-630; sp->c is ic) and the filter, into d_coeffs.
+ * sp->mode none is allowed in both (the plain load and store); abs in spec_blocks only.  Errors: dspfft_motion_last_error. */
+int dspfft_motion_spec_blocks_u8(uint8_t *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                 const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_motion_spec_blocks_f32(float *d_pix, const float *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                  const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_motion_ispec_blocks_u8(float *d_coeffs, const uint8_t *d_pix, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                  const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_motion_ispec_blocks_f32(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
+                                   const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
 /* the float-pixel pair with motion --linear, which the reference applies with --ispec / --spec none (and copy on the store) only:
  * load  pel = sample * 255 (a float product); coeff = (float)(decode(pel / 255) * 255)          (motion.c:623,633)
  * store pel = coeff * scalefactor * normalization; pel *= normalization; sample = (float)(encode(pel / 255) * 255 / 255)   (:759,767-769,774)
