@@ -18,6 +18,7 @@ SYMBOLS = [
     "dspfft_plan_many_r2r_f64", "dspfft_plan_set_scale_f64", "dspfft_plan_set_axis_scale0_f64", "dspfft_execute_f64", "dspfft_execute_masked_accumulate_f64", "dspfft_plan_scan_prepare", "dspfft_plan_set_input_window", "dspfft_plan_set_output_alternate", "dspfft_set_plan_effort", "dspfft_get_plan_effort",
     "dspfft_plan_many_r2r_ordered", "dspfft_plan_guru_r2r", "dspfft_execute_roundtrip", "dspfft_execute_roundtrip_u8", "dspfft_execute_roundtrip_u8_dither",
     "dspfft_execute_spectrogram_u8", "dspfft_execute_spectrogram_f32", "dspfft_execute_ispectrogram_u8", "dspfft_execute_ispectrogram_f32",
+    "dspfft_execute_spec_u8", "dspfft_execute_ispec_u8",
     "dspfft_motion_spec_blocks_u8", "dspfft_motion_spec_blocks_f32", "dspfft_motion_ispec_blocks_u8", "dspfft_motion_ispec_blocks_f32",
     "dspfft_roundtrip_topn_work_bytes", "dspfft_execute_roundtrip_topn", "dspfft_execute_roundtrip_u8_topn", "dspfft_motion_topn_blocks_work_bytes", "dspfft_motion_topn_blocks",
     "dspfft_execute", "dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
@@ -67,6 +68,11 @@ class MotionFilterParams(C.Structure):
 class MotionSpecParams(C.Structure):
     """dspfft_motion_spec_params (include/dspfft.h)"""
     _fields_ = [("mode", C.c_int), ("scalefactor", C.c_double), ("normalization", C.c_double), ("c", C.c_double)]
+
+
+class SpecImageParams(C.Structure):
+    """dspfft_spec_image_params (include/dspfft.h)"""
+    _fields_ = [("gain", C.c_double), ("rangetype", C.c_int), ("scaletype", C.c_int), ("signtype", C.c_int)]
 
 
 _lib = None
@@ -134,6 +140,10 @@ def bind(lib):
         spp, fpp = C.POINTER(MotionSpecParams), C.POINTER(MotionFilterParams)
         lib.dspfft_execute_spectrogram_u8.argtypes = lib.dspfft_execute_spectrogram_f32.argtypes = [vp, vp, vp, vp, spp, fpp, vp, vp]
         lib.dspfft_execute_ispectrogram_u8.argtypes = lib.dspfft_execute_ispectrogram_f32.argtypes = [vp, vp, vp, vp, spp, fpp, C.c_double, vp, vp]
+    if hasattr(lib, "dspfft_execute_spec_u8"):     # (likewise)
+        ipp = C.POINTER(SpecImageParams)
+        lib.dspfft_execute_spec_u8.argtypes = [vp, vp, vp, vp, vp, vp, ipp, vp]
+        lib.dspfft_execute_ispec_u8.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_double), C.c_int, ipp, vp]
     lib.dspfft_plan_set_scale_f64.argtypes = [vp, C.c_double]
     lib.dspfft_plan_set_axis_scale0_f64.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     lib.dspfft_execute_f64.argtypes = [vp, vp, vp, vp]

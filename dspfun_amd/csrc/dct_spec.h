@@ -755,6 +755,82 @@ template <class Re_, int N_, int C_, int T_, int... Rs> using RowSpecT = RowSpec
 template <class Re_, int N_, int G_, int T_, int... Rs> using RowChanSpecT = RowSpecG<Re_, N_, 1, G_, T_, Rs...>;     // one channel of a G_-channel line
 template <int N_, int C_, int T_, int... Rs> using RowSpec = RowSpecT<float, N_, C_, T_, Rs...>;
 
+// The 8-bit ends (U8IO) for INTERLEAVED float lines of C = 3 channels (spec, zoom and scan's RGB lines): the trait row_spec_u8_kernel is
+// instantiated with for them (spec_inst_row_u8c.hip).  B is the line's RowSpec; its stages, its REDFT01 load and its REDFT10 store are B's own,
+// and B itself -- its State<KIND> above all, whose pre[] these ends would lengthen -- is what it was: the plain kernels do not change.
+//  * REDFT10: a thread reads FOUR consecutive pixels, twelve bytes, as three dwords (x = 4 (tid + i T) + q) and writes them to the two slots
+//    of each channel plane that the planar form writes (pixels 4g, 4g + 2 -> slot g; 4g + 3, 4g + 1 -> slot L - 1 - g);
+//  * REDFT01: the same two slots of each plane, read whole, give twelve quantised bytes (quantise_u8_of, as the planar form) in three dwords.
+// The line's byte offset (= its element offset) must be a multiple of 4: the caller checks pointers and strides.
+template <class B>
+struct RowU8Rgb : B {
+	typedef typename B::Re Re;
+	typedef typename B::CX CX;
+	typedef typename B::PA PA;
+	using B::N; using B::C; using B::T; using B::L; using B::NS; using B::PL; using B::K_ROUNDS; using B::LAST_ROUNDS; using B::RL; using B::STW_N; using B::U8_ROUNDS;
+	static_assert(B::C == 3 && B::GS == 3 && B::N % 4 == 0 && std::is_same<Re, float>::value, "interleaved RGB float lines");
+	static constexpr bool U8_OK = true;
+	static constexpr int U8_WAVES = B::WPE;            // min waves per SIMD asked of the register allocator: what the line's plain kernel asks
+	template <int KIND> struct State {
+		CX x[LAST_ROUNDS * RL];
+		Re pre[(KIND == KIND_REDFT10 ? 4 * U8_ROUNDS : 4 * K_ROUNDS) * C];
+		CX tw[K_ROUNDS];
+		CX stw[STW_N > 0 ? STW_N : 1];
+	};
+	template <int KIND, class ST>
+	static DSP_HD void prefetch(const PA &a, long long bin, int tid, ST &st, const U8IO *io)
+	{
+		if constexpr (KIND == KIND_REDFT10) {
+			static_for<0, K_ROUNDS>([&](auto i) {
+				const int k = tid + i * T;
+				if ((i + 1) * T <= L / 2 + 1 || k <= L / 2) st.tw[i] = a.T[k];
+			});
+			static_for<0, U8_ROUNDS>([&](auto i) {
+				const int g = tid + i * T;
+				if ((i + 1) * T <= N / 4 || g < N / 4) {
+					uint32_t w[3];
+					__builtin_memcpy(w, io->in + bin + 12 * g, 12);
+					// byte 3 q + c of the twelve is channel c of pixel 4g + q
+					static_for<0, 12>([&](auto b) { st.pre[i * 12 + b] = (Re)((w[b / 4] >> (8 * (b % 4))) & 0xffu); });
+				}
+			});
+		} else B::template prefetch_m<KIND, false, false>(a, bin, tid, st, nullptr, nullptr);
+	}
+	template <int KIND, int PH, class ST, bool SEQTW = false, bool STW = false, bool TRC = false>
+	static DSP_HD void phase(const PA &a, CX *planes, long long bout, int tid, ST &st, const U8IO *io)
+	{
+		static_assert(!TRC, "no transfer characteristic at these ends");
+		if constexpr (KIND == KIND_REDFT10 && PH == 0) {
+			static_for<0, U8_ROUNDS>([&](auto i) {
+				const int g = tid + i * T;
+				if ((i + 1) * T <= N / 4 || g < N / 4) {
+					static_for<0, C>([&](auto c) {
+						Re v0 = st.pre[i * 12 + c];
+						if constexpr (i == 0) { if (g == 0) v0 *= a.in_scale0; }
+						planes[c * PL + B::padded(g)] = cmk<Re>(v0, st.pre[i * 12 + 6 + c]);
+						planes[c * PL + B::padded(L - 1 - g)] = cmk<Re>(st.pre[i * 12 + 9 + c], st.pre[i * 12 + 3 + c]);
+					});
+				}
+			});
+		} else if constexpr (KIND == KIND_REDFT01 && PH == NS + 2) {
+			const float mulf = (float)io->mul;
+			tloop<N / 4, T>(tid, [&](int g) {
+				uint32_t w[3] = {0, 0, 0};
+				static_for<0, C>([&](auto c) {
+					const CX lo = planes[c * PL + g], hi = planes[c * PL + L - 1 - g];
+					const Re f[4] = {lo.x, -hi.y, -lo.y, hi.x};
+					static_for<0, 4>([&](auto q) {
+						const Re sc = (q == 0 && g == 0) ? a.scale * a.out_scale0 : a.scale;
+						constexpr int b = 3 * q + c;
+						w[b / 4] |= quantise_u8_of(f[q] * sc, io->mul, mulf) << (8 * (b % 4));
+					});
+				});
+				__builtin_memcpy(io->out + bout + 12 * g, w, 12);
+			});
+		} else B::template phase<KIND, PH, ST, SEQTW, STW, false>(a, planes, bout, tid, st, nullptr);
+	}
+};
+
 // =================================================================================================
 DSP_HD int xcd_remap(int bid, int n)
 {

@@ -32,6 +32,7 @@
 #include "block_rs_core.h"
 #include "block_spec_core.h"
 #include "trc_u8_core.h"
+#include "spec_image_core.h"
 
 using namespace dspfft;
 
@@ -72,6 +73,11 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_blocks_la
                                                                                       long long block_stride, const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter,
                                                                                       unsigned long long *d_coeffs_coded, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_row_u8_trc_launch(int row_spec_id, const dspfft::PassArgs *a, const dspfft::U8IOTrc *io, int nwg, void *stream);
+// spec_image.hip's two sweeps and spec_inst_row_u8c.hip's interleaved 8-bit row ends behind dspfft_execute_spec_u8 / _ispec_u8.  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_image_encode_launch(const dspfft::SpecImageEnc *a, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_image_decode_launch(const dspfft::SpecImageDec *a, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_row_u8c_has(int row_spec_id);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_row_u8c_launch(int row_spec_id, const dspfft::PassArgs *a, const dspfft::U8IO *io, int nwg, void *stream);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char *fmt, ...)
@@ -1688,11 +1694,15 @@ namespace {
 // spec_fused.h is_plain, for the host side: none of the fused scan step's or zoom's extras asked for
 bool is_plain_args(const PassArgs &a) { return !a.mask && !a.zflags && !a.accumulate && a.win_hi <= 0 && !a.alt_out && !a.in_mul && !a.in_rev; }
 // a planar row pass that can take / produce 8-bit samples itself
-bool pass_has_u8(const dspfft_plan_s *pl, const Pass &P)
+// rgb: the caller also takes the 8-bit ends of interleaved RGB lines (spec_inst_row_u8c.hip), whose accesses are whole dwords: it has seen to
+// it that every line starts at a multiple of 4 bytes.  The roundtrip and spectrogram calls of motion's planar clips do not ask.
+bool pass_has_u8(const dspfft_plan_s *pl, const Pass &P, bool rgb = false)
 {
-	if (P.type != Pass::ROW || P.pa.C != 1 || !P.hostloop.empty()) return false;
+	if (P.type != Pass::ROW || !P.hostloop.empty()) return false;
 	// the 8-bit kernels are plain instantiations (spec_kernels.h): a plan with zoom's window / modulation / alternating sign on this axis converts separately
 	if (pl->alt_axis == P.axis || (pl->win_axis == P.axis && P.first && pl->zpage)) return false;
+	if (P.pa.C == 3 && rgb) return P.has_spec && !P.jit && dspfft_row_u8c_has && dspfft_row_u8c_launch && dspfft_row_u8c_has(P.spec.id);
+	if (P.pa.C != 1) return false;
 	return (P.has_spec && be_spec_has_u8(P.spec.id)) || (P.jit && P.jit_fn_u8);
 }
 
@@ -1704,6 +1714,10 @@ int run_pass_u8(const dspfft_plan_s *pl, const Pass &P, const float *in, float *
 		U8IO io2 = io;
 		void *args[2] = {&a, &io2};
 		if (int rc = be_jit_launch_n(P.jit_fn_u8, args, P.spec_nwg, P.jit_nthr, stream)) return fail(-4, "kernel launch failed (%s, u8): backend code %d", P.desc.c_str(), rc);
+		return 0;
+	}
+	if (P.pa.C == 3) {        // interleaved RGB lines (pass_has_u8 with rgb)
+		if (int rc = dspfft_row_u8c_launch(P.spec.id, &a, &io, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8 rgb): backend code %d", P.desc.c_str(), rc);
 		return 0;
 	}
 	if (int rc = be_launch_spec_u8(P.spec.id, a, io, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8): backend code %d", P.desc.c_str(), rc);
@@ -2433,6 +2447,95 @@ extern "C" int dspfft_execute_ispectrogram_f32(dspfft_plan inv, const float *d_i
                                                const dspfft_motion_filter_params *fp, double out_mul, unsigned long long *d_coeffs_coded, void *stream)
 {
 	return spec_core(SpecCall{inv, true, false, d_in, d_out, d_work, sp, fp, out_mul, d_coeffs_coded, stream});
+}
+
+// ---- spec / ispec on 8-bit images (include/dspfft.h; the sweeps are spec_image.hip's, their arithmetic spec_image_core.h's) ----
+namespace {
+struct SpecImageCall {
+	dspfft_plan pl; bool inverse;
+	const uint8_t *d_in; uint8_t *d_out; const uint8_t *map_in; uint8_t *map_out;
+	float *d_work; double *d_dc; const double *dc; int restore_dc;
+	const dspfft_spec_image_params *sp; void *stream;
+};
+
+// every rejection comes before the first launch
+int spec_image_core(const SpecImageCall &c)
+{
+	const dspfft_plan pl = c.pl;
+	const char *const what = c.inverse ? "ispec_u8" : "spec_u8";
+	if (!pl || !c.d_in || !c.d_out || !c.sp) return fail(-1, "%s: null plan, buffer or parameters", what);
+	const dspfft_spec_image_params &sp = *c.sp;
+	if (sp.rangetype < 0 || sp.rangetype > 2 || sp.scaletype < 0 || sp.scaletype > 1 || sp.signtype < 0 || sp.signtype > 3 || !(sp.gain == sp.gain) || sp.gain == 0.0)
+		return fail(-1, "%s: bad range / scale / sign code or gain", what);
+	if (pl->f64) return fail(-2, "%s: f64 plans are not implemented", what);
+	const int kind = c.inverse ? DSPFFT_REDFT01 : DSPFFT_REDFT10;
+	if (pl->rank != 2) return fail(-2, "%s: the plan must be of rank 2 (an image), not %d", what, pl->rank);
+	if (pl->kinds[0] != kind || pl->kinds[1] != kind) return fail(-2, "%s: the plan must be %s on both axes", what, c.inverse ? "REDFT01" : "REDFT10");
+	const int h = pl->n[0], w = pl->n[1], d = pl->howmany;
+	std::vector<Dim> dims;
+	for (const Dim &b : pl->batches) if (b.n > 1) dims.push_back(b);
+	merge_dims(dims);
+	const bool chan_ok = dims.empty() ? d == 1 : dims.size() == 1 && dims[0].n == d && dims[0].is == 1 && dims[0].os == 1;
+	if (!chan_ok || pl->axes[1].is != d || pl->axes[1].os != d || pl->axes[0].is != (long long)w * d || pl->axes[0].os != (long long)w * d)
+		return fail(-2, "%s: the plan must be a dense in-place layout of h x w pixels with the channels interleaved (howmany = channels, stride = channels, dist = 1)", what);
+	if (pl->first_axis_first != c.inverse || pl->passes.size() != 2)
+		return fail(-2, "%s: the plan's pass order must be %s", what, c.inverse ? "first axis first (dspfft_plan_many_r2r_ordered(..., 1)): the row pass ends it" : "the default: the row pass begins it");
+	if (d > SPEC_IMAGE_MAX_CH) return fail(-2, "%s: %d channels (the decode handles up to %d)", what, d, (int)SPEC_IMAGE_MAX_CH);
+	if ((c.map_in || c.map_out) && sp.signtype != SPEC_SIGN_ABS) return fail(-2, "%s: a sign map goes with sign type abs only (ispec.c:91)", what);
+	if (c.inverse && (sp.rangetype != SPEC_RANGE_ONE || c.restore_dc) && !c.dc)
+		return fail(-2, "ispec_u8: the DC values from the spectrogram header are required for range dc/dcs and for DC restoration");
+	if (!c.d_work) return fail(-2, "%s: the float work buffer is required", what);
+	if (!dspfft_spec_image_encode_launch || !dspfft_spec_image_decode_launch) return fail(-3, "%s: not built into this library (the kernels are HIP-only, spec_image.hip)", what);
+
+	float *const wk = c.d_work;
+	const uint64_t len = (uint64_t)h * w * d;
+	const std::vector<Pass> &passes = pick_passes(pl, wk, wk);
+	// the 8-bit end on the transform's side rides on the row pass where the plain passes run (execute_t's choice: no block kernel, no split
+	// pair), the pass has the kernel and every line of bytes starts at a multiple of 4
+	const uint8_t *const bytes = c.inverse ? c.d_out : c.d_in;
+	const bool dwords = !(3u & (uintptr_t)bytes) && ((long long)w * d) % 4 == 0;
+	const bool blocky = pl->has_block && !(15u & (uintptr_t)wk);
+	const bool fused8 = !blocky && &passes == &pl->passes && dwords && pass_has_u8(pl, passes[c.inverse ? 1 : 0], true);
+	if (!c.inverse) {
+		if (fused8) {
+			U8IO io; io.in = c.d_in; io.out = nullptr; io.mul = 1.0;
+			if (int rc = run_pass_u8(pl, passes[0], wk, wk, false, io, c.stream)) return rc;
+			if (int rc = run_pass<float>(pl, passes[1], (const float *)wk, wk, true, c.stream)) return rc;
+		} else {
+			if (be_u8_to_f32(wk, c.d_in, len, c.stream)) return fail(-4, "launch failed");
+			if (int rc = execute_t<float>(pl, wk, wk, c.stream)) return rc;
+		}
+		SpecImageEnc e;
+		e.f = wk; e.out = c.d_out; e.signmap = c.map_out; e.dc = c.d_dc; e.len = len; e.d = d;
+		e.gain = sp.gain; e.rangetype = sp.rangetype; e.scaletype = sp.scaletype; e.signtype = sp.signtype;
+		if (dspfft_spec_image_encode_launch(&e, c.stream)) return fail(-4, "spec_u8: launch failed");
+		return 0;
+	}
+	SpecImageDec e;
+	e.in = c.d_in; e.signmap = c.map_in; e.f = wk; e.len = len; e.d = d;
+	e.gain = sp.gain; e.scaletype = sp.scaletype; e.signtype = sp.signtype; e.restore_dc = c.restore_dc ? 1 : 0;
+	for (int z = 0; z < SPEC_IMAGE_MAX_CH; z++) { e.mx[z] = 0; e.dc[z] = c.dc && z < d ? c.dc[z] : 0; }
+	spec_image_decode_max(e.mx, e.dc, d, sp.gain, sp.rangetype, sp.scaletype);
+	if (dspfft_spec_image_decode_launch(&e, c.stream)) return fail(-4, "ispec_u8: launch failed");
+	if (fused8) {
+		if (int rc = run_pass<float>(pl, passes[0], (const float *)wk, wk, false, c.stream)) return rc;
+		U8IO io; io.in = nullptr; io.out = c.d_out; io.mul = 255.0;
+		return run_pass_u8(pl, passes[1], wk, wk, true, io, c.stream);
+	}
+	if (int rc = execute_t<float>(pl, wk, wk, c.stream)) return rc;
+	return be_f32_to_u8(c.d_out, wk, 255.0, len, c.stream) ? fail(-4, "launch failed") : 0;
+}
+}  // namespace
+
+extern "C" int dspfft_execute_spec_u8(dspfft_plan fwd, const uint8_t *d_in, uint8_t *d_out, uint8_t *d_signmap, float *d_work, double *d_dc,
+                                      const dspfft_spec_image_params *sp, void *stream)
+{
+	return spec_image_core(SpecImageCall{fwd, false, d_in, d_out, nullptr, d_signmap, d_work, d_dc, nullptr, 0, sp, stream});
+}
+extern "C" int dspfft_execute_ispec_u8(dspfft_plan inv, const uint8_t *d_in, const uint8_t *d_signmap, uint8_t *d_out, float *d_work, const double *dc,
+                                       int restore_dc, const dspfft_spec_image_params *sp, void *stream)
+{
+	return spec_image_core(SpecImageCall{inv, true, d_in, d_out, d_signmap, nullptr, d_work, nullptr, dc, restore_dc, sp, stream});
 }
 
 extern "C" size_t dspfft_roundtrip_topn_work_bytes(dspfft_plan fwd, dspfft_plan inv)

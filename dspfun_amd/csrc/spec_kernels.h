@@ -300,7 +300,10 @@ int launch_czt_spectrum(const CztArgs &a, cf *hspec, void *stream)
 // kernel alone: 896 -> 813 us; 74 -> 64 VGPRs, no scratch).  Asked where the kernel FITS 64 registers: longer lines keep the allocator's choice (at 64 they spill), and
 // `make -C dspfun_amd/csrc check-scratch` fails on scratch in these kernels.  (960-sample REDFT10 lines spilled 12 bytes a lane beside the radix-16 butterfly of their
 // round-5 radices (2, 16, 15) and ran at six waves; with (4, 8, 15) they fit -- six or eight waves measure the same, 3.91-3.94 ms per clip.)
-template <class S, int KIND> constexpr int u8_waves_per_simd() { return S::N >= 2048 ? S::WPE : 8; }
+// (a spec that names its own figure, U8_WAVES, gets it: the interleaved RGB ends of dct_spec.h RowU8Rgb ask what their plain kernels ask)
+template <class S> constexpr auto u8_waves_named(int) -> decltype(S::U8_WAVES) { return S::U8_WAVES; }
+template <class S> constexpr int u8_waves_named(long) { return 0; }
+template <class S, int KIND> constexpr int u8_waves_per_simd() { return u8_waves_named<S>(0) ? u8_waves_named<S>(0) : S::N >= 2048 ? S::WPE : 8; }
 template <class S, int KIND>
 __global__ void __launch_bounds__(S::T, (u8_waves_per_simd<S, KIND>())) row_spec_u8_kernel(const typename S::PA a_, const U8IO io_)
 {

@@ -252,6 +252,20 @@ class Plan:
         self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), C.byref(fp) if fp is not None else None,
                         mul, C.c_void_p(d_coded or None), C.c_void_p(stream)))
 
+    def spec_u8(self, d_in, d_out, d_work, params, d_signmap=0, d_dc=0, stream=0):
+        """spec on an 8-bit image in device memory (dspfft_execute_spec_u8): bytes -> self (the forward plan of spec_image_plans) -> display
+        encoding -> bytes, in three sweeps.  params: spec_image_params(...).  d_signmap (abs only): also the `sign` preset's image, what
+        ispec -m reads; d_dc: `channels` doubles on the device, the header's DC values."""
+        self._check(self._lib.dspfft_execute_spec_u8(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_signmap or None), C.c_void_p(d_work or None),
+                                                     C.c_void_p(d_dc or None), C.byref(params), C.c_void_p(stream)))
+
+    def ispec_u8(self, d_in, d_out, d_work, params, d_signmap=0, dc=None, restore_dc=False, stream=0):
+        """ispec on an 8-bit spectrogram in device memory (dspfft_execute_ispec_u8): bytes (+ sign map) -> decoding -> self (the inverse
+        plan of spec_image_plans) -> bytes.  dc: the header's DC values (host floats), needed for range dc / dcs and for restore_dc."""
+        dcp = None if dc is None else (C.c_double * len(dc))(*[float(v) for v in dc])
+        self._check(self._lib.dspfft_execute_ispec_u8(self._h, C.c_void_p(d_in), C.c_void_p(d_signmap or None), C.c_void_p(d_out), C.c_void_p(d_work or None),
+                                                      dcp, int(bool(restore_dc)), C.byref(params), C.c_void_p(stream)))
+
     def describe(self):
         buf = C.create_string_buffer(4096)
         self._check(self._lib.dspfft_plan_describe(self._h, buf, len(buf)))
@@ -398,6 +412,45 @@ _MOTION_MODES = {"none": 0, "abs": 1, "shift": 2, "flat": 3, "copy": 4}
 def _spec_params(mode, scalefactor, normalization, c=None):
     m = _MOTION_MODES[mode] if isinstance(mode, str) else int(mode)
     return _lib.MotionSpecParams(m, float(scalefactor), float(normalization), 0.0 if c is None else float(c))
+
+
+def spec_image_plans(h, w, c, lib=None):
+    """The plan pair of Plan.spec_u8 / Plan.ispec_u8 for an h x w image of c interleaved channels: REDFT10 with spec.c:70-78's normalisation
+    of (float)byte (scale 1 / (255 * 2wh), 1 / sqrt 2 at index 0 of both axes) and REDFT01, row pass last, with ispec.c:153-159's factors."""
+    import math
+    r2 = math.sqrt(2.0)
+    fwd = Plan.image(h, w, c, REDFT10, lib=lib).set_scale(1.0 / (255.0 * 2.0 * w * h))
+    inv = Plan.many_r2r([h, w], [REDFT01, REDFT01], howmany=c, istride=c, idist=1, ostride=c, odist=1, lib=lib, first_axis_first=True).set_scale(0.5)
+    for a in range(2):
+        fwd.set_axis_scale0(a, 1.0, 1.0 / r2)
+        inv.set_axis_scale0(a, r2, 1.0)
+    return fwd, inv
+
+
+SPEC_IMAGE_RANGES = {"one": 0, "dc": 1, "dcs": 2}
+SPEC_IMAGE_SCALES = {"log": 0, "linear": 1}
+SPEC_IMAGE_SIGNS = {"abs": 0, "shift": 1, "saturate": 2, "retain": 3}
+#: spec -t (spec/spec.h:71-79): scale, sign, gain, range
+SPEC_IMAGE_PRESETS = {"abs": ("log", "abs", "native", "dc"), "shift": ("log", "shift", "native", "one"), "flat": ("linear", "shift", "custom", "one"),
+                      "sign": ("linear", "saturate", "custom", "one"), "copy": ("linear", "retain", "custom", "one")}
+
+
+def spec_image_params(h, w, preset="abs", range=None, scale=None, sign=None, gain=None):
+    """dspfft_spec_image_params from spec's options: preset is -t, and range (-R), scale (-T), sign (-S) and gain (-G: "native" =
+    127.5 sqrt(4wh), "reference" = 127.5 * 1024, or a number; a preset's "custom" is 1) replace what it sets."""
+    import math
+    sc, sg, gn, rg = SPEC_IMAGE_PRESETS[preset]
+    rg, sc, sg = range or rg, scale or sc, sign or sg
+    gn = gn if gain is None else gain
+    if gn == "native":
+        g = 127.5 * math.sqrt(w * h * 4)
+    elif gn == "reference":
+        g = 127.5 * 1024
+    elif gn == "custom":
+        g = 1.0
+    else:
+        g = float(gn)
+    return _lib.SpecImageParams(g, SPEC_IMAGE_RANGES[rg], SPEC_IMAGE_SCALES[sc], SPEC_IMAGE_SIGNS[sg])
 
 
 def motion_spec_constants(block, scaled=None):

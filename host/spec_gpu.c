@@ -2,8 +2,8 @@
  * spec_gpu / ispec_gpu -- plain-C harness reproducing the transform core of the reference's
  * `spec` (spec/spec.c:59-78) and `ispec` (spec/ispec.c:153-167) over the FFTW-named API of
  * include/fftw3.h, i.e. exactly the calls the tools make, served by the MI355X engine.
- * Only the "-t copy" (retain sign, linear, gain 1... i.e. no display encoding) path is reproduced:
- * the display encodings of spec.c:81-139 are elementwise host code outside the hot path.
+ * Only the "-t copy" (retain sign, linear, gain 1... i.e. no display encoding) path is reproduced here, on float files: the display
+ * encodings of spec.c:81-139 and their 8-bit images run on the device in host/spec_dev.c (dspfft_execute_spec_u8 / _ispec_u8).
  *
  *   spec_gpu  spec  in.{ppm,pf} out.pf     uniform-range coefficients in [-1,1]
  *   spec_gpu  ispec in.pf       out.pf     image back

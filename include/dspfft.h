@@ -393,6 +393,34 @@ int dspfft_execute_ispectrogram_u8(dspfft_plan inv, const uint8_t *d_in, uint8_t
 int dspfft_execute_ispectrogram_f32(dspfft_plan inv, const float *d_in, float *d_out, float *d_work, const dspfft_motion_spec_params *sp,
                                     const dspfft_motion_filter_params *filter, double out_mul, unsigned long long *d_coeffs_coded, void *hip_stream);
 
+/* spec and ispec on 8-bit images (spec/spec.c:63-139 and spec/ispec.c:84-167 with an 8-bit reader and writer) as one call each way, device
+ * memory to device memory:
+ *   spec_u8   bytes -> REDFT10 over h x w with `channels` interleaved signals -> display encoding (dspfft_spec_encode's codes; the divisors
+ *             come from the first pixel on the device) -> bytes clamp(lround(255 e)).  d_signmap (NULL ok; sign type abs only): the same
+ *             sweep also writes the `sign` preset's bytes (spec.h:75: linear, saturate, range one, gain 1), the companion image ispec -m
+ *             reads.  d_dc (device, NULL ok): the `channels` doubles of the header's "DC" property (spec.c:66-68).
+ *   ispec_u8  bytes (b / 255 as the reader gives it) [+ sign map, ispec.c:91-95] -> unsign, unscale, / gain, optional DC restore (dc: host
+ *             memory, as dspfft_ispec_decode's; needed for range dc / dcs and for restore_dc) -> REDFT01 -> bytes quantise(255 p).
+ * The plans are the caller's and carry the normalisation: `fwd` a dense in-place f32 plan of rank 2 in the default pass order with scale
+ * 1 / (255 * 2wh) and 1 / sqrt 2 at output index 0 of both axes (spec.c:70-78 on (float)byte); `inv` the REDFT01 plan made with
+ * dspfft_plan_many_r2r_ordered(..., 1), so that the row pass ends it, with ispec.c:153-159's factors (sqrt 2 at input index 0 of both axes,
+ * scale 1/2).  Both: howmany = channels (<= 4), stride = channels, dist = 1.
+ * Sweeps: the row pass reads (writes) the bytes itself where it has an 8-bit end -- planar lines and the interleaved RGB lines of 3840,
+ * 1920, 7680, 960, 512 and 256 pixels, with the image 4-byte aligned and w * channels a multiple of 4; dspfft_u8_to_f32 / dspfft_f32_to_u8
+ * otherwise (runtime-geometry lines, other channel counts, plans with a window, modulation or alternating sign, frames that run on the
+ * split passes) -- then the column pass in d_work and ONE sweep for the encoding and its store (or, first, the load and its decoding).
+ * The bytes, the sign map and the DC values are those of dspfft_u8_to_f32 -> dspfft_execute -> dspfft_spec_encode -> dspfft_f32_to_u8(255)
+ * (once more with the sign preset), and of the upload of b / 255 -> dspfft_ispec_signmap -> dspfft_ispec_decode -> dspfft_execute ->
+ * dspfft_f32_to_u8(255).  d_in == d_out is allowed.  Stream-ordered, no allocation: both calls can sit in a captured graph.
+ * Refused with -2, the reason in dspfft_last_error and nothing launched: an f64 plan, a plan of another rank, kind, layout or pass order,
+ * more than 4 channels, a sign map with a sign type other than abs, range dc / dcs or restore_dc without dc, d_work == NULL.  -3 from a
+ * library built without the HIP kernels. */
+typedef struct { double gain; int rangetype, scaletype, signtype; } dspfft_spec_image_params;   /* codes as dspfft_spec_encode */
+int dspfft_execute_spec_u8(dspfft_plan fwd, const uint8_t *d_in, uint8_t *d_out, uint8_t *d_signmap, float *d_work, double *d_dc,
+                           const dspfft_spec_image_params *sp, void *hip_stream);
+int dspfft_execute_ispec_u8(dspfft_plan inv, const uint8_t *d_in, const uint8_t *d_signmap, uint8_t *d_out, float *d_work, const double *dc,
+                            int restore_dc, const dspfft_spec_image_params *sp, void *hip_stream);
+
 /* Replaces fftw(destroy_plan). */
 void dspfft_destroy_plan(dspfft_plan plan);
 
