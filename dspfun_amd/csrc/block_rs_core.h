@@ -16,6 +16,7 @@
 // Every extent is 4, 8, 16 or 32 (a power of two: the index arithmetic shifts).  The tile geometry is run-time; only the line functions
 // are templates, on <N, S>, and the two ends on <N, 8-bit, table>, each chosen by a switch that is uniform over the workgroup.
 // Plain C++17 for device (hipcc) and host (g++: tests/test_motion_block_rescale_cpu.py runs the phases thread by thread).
+// At the end of the file: the further phases of the same grid with motion --coeff-limit (block_rescale_topn.hip).
 #pragma once
 #include "block_core.h"
 
@@ -264,5 +265,152 @@ DSP_HD void rs_phase_store(const RsTile &a, const float *lds, long long bout, in
 #undef DSP_RS_CASE
 	}
 }
+
+// ---- motion --coeff-limit on a rescaled grid (block_rescale_topn.hip; motion.c:652-668 ranks the whole M embedding) ----
+// The reference multiplies only the A corner by the uniform-range factors (:644-647) and then ranks every element of the embedding, so an
+// element inside N but outside A competes with its RAW coefficient.  The forward passes here are the pruned kernel's, with the plan's scales
+// in the butterflies, over ALL of N; the last of them rewrites what it stores outside A as the value the reference ranks: the scales divided
+// out again, times `outside_mul`.  Nothing reads those elements after the selection, so they are keys only.  The selection itself is
+// topn_core.h's on the tile; behind it the filter and the inverse passes read A alone, as the pruned kernel's do.
+struct BlockRsTopnArgs : BlockRsArgs {
+	unsigned int keep;            // 0 < keep < MX MY MZ
+	float key_mul;                // outside_mul / f.scale ...
+	float key_mul0[3];            // ... and per axis (x, y, z) 1 / f.out0[axis], for index 0 of that axis
+};
+// what the phases below read of them
+struct RsKeys { float mul, mul0[3]; };
+DSP_HD RsKeys rs_keys_of(const BlockRsTopnArgs &a)
+{
+	RsKeys k;
+	k.mul = a.key_mul;
+	for (int i = 0; i < 3; i++) k.mul0[i] = a.key_mul0[i];
+	return k;
+}
+// The tile as the unpruned forward phases see it: with `scaled` = the embedding, rs_phase_load stores all NX results of a line and
+// rs_phase_fwd_y runs over all columns x < NX and stores all NY results (min(N, M) = N).
+DSP_HD RsTile rs_tile_unpruned(const RsTile &a)
+{
+	RsTile t = a;
+	t.ox = rs_max(a.nx, a.ox); t.oy = rs_max(a.ny, a.oy); t.oz = rs_max(a.nz, a.oz);
+	return t;
+}
+// zeros where the embedding lies outside N (upscaled axes): the selection reads every element of the embedding.  Runs beside the load,
+// which writes inside N only.
+DSP_HD void rs_phase_zero_outside(const RsTile &a, float *lds, int cnt, int tid)
+{
+	const int my = rs_max(a.ny, a.oy), mz = rs_max(a.nz, a.oz);
+	if (a.tw == a.nx && my == a.ny && mz == a.nz) return;
+	const int lqx = rs_log2(a.tw) - 2, lmy = rs_log2(my), total = (mz * my * cnt) << lqx;
+	for (int l = tid; l < total; l += BLOCK_THREADS) {
+		const int q = l & ((1 << lqx) - 1), t = l >> lqx, row = t / cnt, g = t - row * cnt;
+		if (4 * q >= a.nx || (row & (my - 1)) >= a.ny || (row >> lmy) >= a.nz) {
+			float4 v; v.x = v.y = v.z = v.w = 0.f;
+			*reinterpret_cast<float4 *>(lds + row * a.pitch + g * a.tw + 4 * q) = v;
+		}
+	}
+}
+// REDFT10 over N, all N results stored; in_a: the column lies inside A on the other axes, and then the first min(N, S) results are the
+// coefficients; every other result becomes its key value (mul; mul0 at index 0)
+template <int N, int S>
+DSP_HD void rs_line_fwd_keys(const TinyArgs &t, float *p, int stride, bool in_a, float mul, float mul0)
+{
+	constexpr int A = N < S ? N : S;
+	float x[N], o[N];
+#pragma unroll
+	for (int j = 0; j < N; j++) x[j] = p[j * stride];
+	tiny_dct<N, KIND_REDFT10>(t, x, o);
+#pragma unroll
+	for (int j = 0; j < N; j++) p[j * stride] = (in_a && j < A) ? o[j] : o[j] * (j == 0 ? mul0 : mul);
+}
+// the filter over the first min(N, S) values of a line and REDFT01 over S: rs_line_mid without its forward half
+template <int N, int S, bool ZAXIS>
+DSP_HD void rs_line_filt_inv(const TinyArgs &ti, const MotionFilter &f, float *p, int stride, int o, int bx, unsigned long long &coded)
+{
+	constexpr int A = N < S ? N : S;
+	float w[S], r[S];
+#pragma unroll
+	for (int j = 0; j < S; j++) w[j] = j < A ? p[j * stride] : 0.f;
+	if (f.enabled) {
+#pragma unroll
+		for (int j = 0; j < A; j++) {
+			const int bz = ZAXIS ? j : o, by = ZAXIS ? o : j;
+			if (bx < f.aw && by < f.ah && bz < f.ad) w[j] = motion_filter_at(f, bz, by, bx, w[j], coded);
+		}
+	}
+	tiny_dct<S, KIND_REDFT01>(ti, w, r);
+#pragma unroll
+	for (int j = 0; j < S; j++) p[j * stride] = r[j];
+}
+// the last forward axis (z; y for 2-D blocks) over all columns x < NX (, y < NY), with the forward plan's global scale as in rs_phase_mid
+DSP_HD void rs_phase_fwd_last_keys(const RsTile &a, const RsKeys &k, float *lds, int cnt, int tid)
+{
+	const int lnx = rs_log2(a.nx), ax = rs_min(a.nx, a.ox), my = rs_max(a.ny, a.oy);
+	if (a.nz > 1) {
+		const TinyArgs tf = block_axis_args(a.f, 2, true);
+		const int total = a.ny * cnt * a.nx, ay = rs_min(a.ny, a.oy);
+		switch (a.nz * 64 + a.oz) {
+#define DSP_RS_CASE(N_, S_) \
+		case N_ * 64 + S_: \
+			for (int l = tid; l < total; l += BLOCK_THREADS) { \
+				int o, bx; float *p = lds + rs_col(a, l, lnx, cnt, a.pitch, o, bx); \
+				const float m = k.mul * (bx ? 1.f : k.mul0[0]) * (o ? 1.f : k.mul0[1]); \
+				rs_line_fwd_keys<N_, S_>(tf, p, my * a.pitch, bx < ax && o < ay, m, m * k.mul0[2]); } \
+			break;
+		DSPFFT_RS_PAIRS16(DSP_RS_CASE)
+#undef DSP_RS_CASE
+		}
+	} else {
+		const TinyArgs tf = block_axis_args(a.f, 1, true);
+		const int total = cnt * a.nx;
+		switch (a.ny * 64 + a.oy) {
+#define DSP_RS_CASE(N_, S_) \
+		case N_ * 64 + S_: \
+			for (int l = tid; l < total; l += BLOCK_THREADS) { \
+				int o, bx; float *p = lds + rs_col(a, l, lnx, cnt, 0, o, bx); \
+				const float m = k.mul * (bx ? 1.f : k.mul0[0]) * k.mul0[2]; \
+				rs_line_fwd_keys<N_, S_>(tf, p, a.pitch, bx < ax, m, m * k.mul0[1]); } \
+			break;
+		DSPFFT_RS_PAIRS32(DSP_RS_CASE)
+#undef DSP_RS_CASE
+		}
+	}
+}
+// behind the selection: the filter and the inverse's first axis over A, rs_phase_mid's columns
+DSP_HD void rs_phase_filt_inv_last(const RsTile &a, float *lds, int cnt, int tid, unsigned long long &coded)
+{
+	const int kx = rs_min(a.nx, a.ox), lkx = rs_log2(kx), my = rs_max(a.ny, a.oy);
+	if (a.nz > 1) {
+		const TinyArgs ti = block_axis_args(a.i, 2, false);
+		const int total = rs_min(a.ny, a.oy) * cnt * kx;
+		switch (a.nz * 64 + a.oz) {
+#define DSP_RS_CASE(N_, S_) \
+		case N_ * 64 + S_: \
+			for (int l = tid; l < total; l += BLOCK_THREADS) { int o, bx; float *p = lds + rs_col(a, l, lkx, cnt, a.pitch, o, bx); rs_line_filt_inv<N_, S_, true>(ti, a.filt, p, my * a.pitch, o, bx, coded); } \
+			break;
+		DSPFFT_RS_PAIRS16(DSP_RS_CASE)
+#undef DSP_RS_CASE
+		}
+	} else {
+		const TinyArgs ti = block_axis_args(a.i, 1, false);
+		const int total = cnt * kx;
+		switch (a.ny * 64 + a.oy) {
+#define DSP_RS_CASE(N_, S_) \
+		case N_ * 64 + S_: \
+			for (int l = tid; l < total; l += BLOCK_THREADS) { int o, bx; float *p = lds + rs_col(a, l, lkx, cnt, 0, o, bx); rs_line_filt_inv<N_, S_, false>(ti, a.filt, p, a.pitch, 0, bx, coded); } \
+			break;
+		DSPFFT_RS_PAIRS32(DSP_RS_CASE)
+#undef DSP_RS_CASE
+		}
+	}
+}
+// the selection's geometry: a block's embedding has E = MX MY MZ elements (16 ... 4096, a power of two), L = min(E, 64) lanes hold K = E / L
+// keys each; the <K, MX> with a selection: X(K, MX)
+#define DSPFFT_RS_TOPN_SHAPES(X) \
+	X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) \
+	X(1, 8) X(2, 8) X(4, 8) X(8, 8) X(16, 8) X(32, 8) \
+	X(1, 16) X(2, 16) X(4, 16) X(8, 16) X(16, 16) X(32, 16) X(64, 16) \
+	X(2, 32) X(4, 32) X(8, 32) X(16, 32)
+DSP_HD int rs_topn_elems(const RsTile &a) { return a.tw * rs_max(a.ny, a.oy) * rs_max(a.nz, a.oz); }
+DSP_HD int rs_topn_keys(int E) { return E >= 64 ? E / 64 : 1; }
 
 }  // namespace dspfft

@@ -7,8 +7,8 @@
 
 namespace dspfft {
 
-// OUT8 = false: the dithered roundtrip, whose bytes the dither kernel stores from the float result (no call combines it with a coefficient
-// limit: that pair is not instantiated)
+// OUT8 = false: the dithered roundtrip, whose bytes the dither kernel stores from the float result (with a coefficient limit:
+// dspfft_execute_roundtrip_u8_dither_limit)
 template <int NX, int NY, int NZ, bool OUT8, bool TOPN>
 static auto block_trc_kernel()
 {
@@ -38,7 +38,7 @@ extern "C" __attribute__((visibility("hidden"))) int dspfft_block_trc_launch(con
 	lds += sizeof(TrcU8Tab);
 #define DSP_BLOCK_CASE(X_, Y_, Z_) \
 	if (a.nx == X_ && a.ny == Y_ && a.nz == Z_) { \
-		if (a.keep) return a.out8 ? launch_block_rt_trc<X_, Y_, Z_, true, true>(a, nwg, lds, stream) : -1; \
+		if (a.keep) return a.out8 ? launch_block_rt_trc<X_, Y_, Z_, true, true>(a, nwg, lds, stream) : launch_block_rt_trc<X_, Y_, Z_, false, true>(a, nwg, lds, stream); \
 		return a.out8 ? launch_block_rt_trc<X_, Y_, Z_, true, false>(a, nwg, lds, stream) : launch_block_rt_trc<X_, Y_, Z_, false, false>(a, nwg, lds, stream); \
 	}
 	DSPFFT_BLOCK_SHAPES(DSP_BLOCK_CASE)

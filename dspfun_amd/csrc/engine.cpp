@@ -67,6 +67,8 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_trc_lau
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_trc_launch(const dspfft::BlockRtTrcArgs *a, int nwg, size_t lds, void *stream);
 // block_rescale.hip's launcher behind a roundtrip over a rescaled block grid (motion -b with -s).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_launch(const dspfft::BlockRsArgs *a, int nwg, size_t lds, void *stream);
+// block_rescale_topn.hip's launcher behind the same with a coefficient limit (dspfft_execute_roundtrip_limit and its kin).  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_topn_launch(const dspfft::BlockRsTopnArgs *a, int nwg, size_t lds, void *stream);
 // block_spec.hip's and motion_ops.hip's launchers behind dspfft_execute_spectrogram_* / _ispectrogram_*.  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_spec_launch(const dspfft::BlockSpecArgs *a, int inverse, int nwg, size_t lds, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_blocks_launch(int inverse, int u8, void *d_pix, void *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks,
@@ -1767,7 +1769,7 @@ int dither_store(const dspfft_plan_s *inv, const float *work, const Dither &dz, 
 }
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
                    const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice = true,
-                   const Dither *dither = nullptr, size_t keep = 0, void *topn_work = nullptr, size_t topn_work_bytes = 0);
+                   const Dither *dither = nullptr, size_t keep = 0, void *topn_work = nullptr, size_t topn_work_bytes = 0, double outside_mul = 0.0);
 
 // ---- the fused roundtrip: one call, checked (rt_check), then run by one of four strategies (roundtrip_core) ----
 // DSPFFT_NO_FUSED_ROUNDTRIP=1: no fused column kernel and no slices.  Read on every call (tests toggle it inside one process).
@@ -1797,6 +1799,7 @@ struct RtCall {
 	const float *d_in; float *d_out; const uint8_t *d_in8; uint8_t *d_out8; double mul8;
 	const dspfft_motion_filter_params *fp; unsigned long long *coded; void *stream;
 	size_t keep; void *topn_work; size_t topn_work_bytes;       // motion --coeff-limit (dspfft_execute_roundtrip_topn); keep = 0: none
+	double outside_mul;                   // > 0: the call came through a dspfft_execute_roundtrip*_limit entry, which takes a limit on a rescaled block grid
 	// what rt_check adds (zero before)
 	const Pass *F, *I;                    // the forward plan's last pass and the inverse plan's first
 	bool rescale;                         // the inverse runs over other extents than the forward
@@ -1812,6 +1815,7 @@ struct RtCall {
 	bool grid;                            // a rescaled block grid (rt_grid): block_rescale.hip's kernel runs the call, out of place
 	BlockRsArgs rs;                       // its arguments, with the geometry derived for the pair
 	int rs_nwg; size_t rs_lds;
+	size_t rs_keep;                       // ... and its coefficient limit (0: none; block_rescale_topn.hip's kernel otherwise)
 };
 // the conversions at the ends of the unfused paths, plain or through the call's transfer characteristic
 int rt_u8_in(const RtCall &c, float *dst, uint64_t len)
@@ -1881,8 +1885,13 @@ int rt_grid(RtCall &c)
 	if (!same || fwd->howmany != inv->howmany) return fail(-2, "%s: the plans count different numbers of blocks", what);
 	if (!dspfft_block_rescale_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale.hip)", what);
 	const int mx = std::max(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
-	if (c.keep && c.keep < (size_t)mx * my * mz)
-		return fail(-2, "%s: a coefficient limit is not implemented here (the reference selects over the whole embedding, motion.c:652-668)", what);
+	if (c.keep && c.keep < (size_t)mx * my * mz) {
+		// (the entries without dspfft_coeff_limit have no outside_mul to rank the coefficients outside min(block, scaled) with)
+		if (!(c.outside_mul > 0))
+			return fail(-2, "%s: a coefficient limit is not implemented here (the reference selects over the whole embedding, motion.c:652-668)", what);
+		if (!dspfft_block_rescale_topn_launch) return fail(-3, "%s with a coefficient limit: not built into this library (the kernel is HIP-only, block_rescale_topn.hip)", what);
+		c.rs_keep = c.keep;
+	}
 	c.keep = 0;
 	if (!rt_ends_aligned(c)) return fail(-2, "%s: float buffers must be 16-byte aligned, 8-bit buffers 4-byte aligned", what);
 	if (int rc = rt_filter(c)) return rc;
@@ -1917,6 +1926,17 @@ int rt_grid(RtCall &c)
 // into the inverse plan's output layout
 int rt_run_grid(const RtCall &c)
 {
+	if (c.rs_keep) {
+		// what the reference ranks outside min(block, scaled): the coefficient without the forward plan's scales, times outside_mul (block_rs_core.h)
+		BlockRsTopnArgs t;
+		memset((void *)&t, 0, sizeof t);
+		static_cast<BlockRsArgs &>(t) = c.rs;
+		t.keep = (unsigned int)c.rs_keep;
+		t.key_mul = (float)(c.outside_mul / (double)c.rs.f.scale);
+		for (int k = 0; k < 3; k++) t.key_mul0[k] = 1.f / c.rs.f.out0[k];
+		if (int rc = dspfft_block_rescale_topn_launch(&t, c.rs_nwg, c.rs_lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid with a coefficient limit): backend code %d", rc);
+		return 0;
+	}
 	if (int rc = dspfft_block_rescale_launch(&c.rs, c.rs_nwg, c.rs_lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid): backend code %d", rc);
 	return 0;
 }
@@ -2275,9 +2295,9 @@ int roundtrip_sliced(const RtCall &c, const Dither *dither)
 // dither non-NULL (d_out8 NULL): the inverse transform ends in d_out as floats and the dither kernel stores dither->out8 from there.
 int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
                    const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice, const Dither *dither,
-                   size_t keep, void *topn_work, size_t topn_work_bytes)
+                   size_t keep, void *topn_work, size_t topn_work_bytes, double outside_mul)
 {
-	RtCall c = {fwd, inv, d_in, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream, keep, topn_work, topn_work_bytes};
+	RtCall c = {fwd, inv, d_in, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream, keep, topn_work, topn_work_bytes, outside_mul};
 	c.dithered = dither != nullptr;
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
@@ -2560,9 +2580,10 @@ extern "C" int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv
 	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream, true, nullptr, keep, d_topn_work, work_bytes);
 }
 
-extern "C" int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
-                                                  double scalefactor, double normalization, const dspfft_motion_filter_params *fp,
-                                                  unsigned long long *d_coeffs_coded, void *stream)
+namespace {
+// dspfft_execute_roundtrip_u8_dither and its twin with a coefficient limit (cl NULL: none)
+int roundtrip_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double scalefactor, double normalization,
+                     const dspfft_motion_filter_params *fp, const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
 {
 	if (!fwd || !inv || !d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the dithered roundtrip takes f32 plans");
@@ -2571,7 +2592,48 @@ extern "C" int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan i
 	dspfft_dither_geom g;
 	if (int rc = dither_geom_of(inv, g)) return rc;
 	const Dither dz = {d_out, scalefactor, normalization};
-	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, nullptr, 1.0, fp, d_coeffs_coded, stream, true, &dz);
+	if (!cl) return roundtrip_core(fwd, inv, nullptr, d_work, d_in, nullptr, 1.0, fp, d_coeffs_coded, stream, true, &dz);
+	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, nullptr, 1.0, fp, d_coeffs_coded, stream, true, &dz, cl->keep, cl->d_work, cl->work_bytes, cl->outside_mul);
+}
+// what every dspfft_execute_roundtrip*_limit entry refuses of its dspfft_coeff_limit
+int coeff_limit_check(const dspfft_coeff_limit *cl)
+{
+	if (!cl) return fail(-1, "coefficient limit: null dspfft_coeff_limit (the entries without one take none)");
+	if (!cl->keep) return fail(-1, "coefficient limit: keep must be at least 1 (the entries without a dspfft_coeff_limit take none)");
+	if (!std::isfinite(cl->outside_mul) || !(cl->outside_mul > 0)) return fail(-1, "coefficient limit: outside_mul must be finite and > 0 (1 for motion's 3-D blocks)");
+	return 0;
+}
+}  // namespace
+
+extern "C" int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
+                                                  double scalefactor, double normalization, const dspfft_motion_filter_params *fp,
+                                                  unsigned long long *d_coeffs_coded, void *stream)
+{
+	return roundtrip_dither(fwd, inv, d_in, d_out, d_work, scalefactor, normalization, fp, nullptr, d_coeffs_coded, stream);
+}
+
+extern "C" int dspfft_execute_roundtrip_limit(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const dspfft_motion_filter_params *fp,
+                                              const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (int rc = coeff_limit_check(cl)) return rc;
+	if (!d_in) return fail(-1, "null plan or buffer");
+	return roundtrip_core(fwd, inv, d_in, d_out, nullptr, nullptr, 1.0, fp, d_coeffs_coded, stream, true, nullptr, cl->keep, cl->d_work, cl->work_bytes, cl->outside_mul);
+}
+
+extern "C" int dspfft_execute_roundtrip_u8_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
+                                                 const dspfft_motion_filter_params *fp, const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (int rc = coeff_limit_check(cl)) return rc;
+	if (!d_in || !d_out) return fail(-1, "null plan or buffer");
+	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream, true, nullptr, cl->keep, cl->d_work, cl->work_bytes, cl->outside_mul);
+}
+
+extern "C" int dspfft_execute_roundtrip_u8_dither_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
+                                                        double scalefactor, double normalization, const dspfft_motion_filter_params *fp,
+                                                        const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (int rc = coeff_limit_check(cl)) return rc;
+	return roundtrip_dither(fwd, inv, d_in, d_out, d_work, scalefactor, normalization, fp, cl, d_coeffs_coded, stream);
 }
 
 extern "C" int dspfft_scan_zigzag_frame_ids(uint32_t *d_ids, uint32_t w, uint32_t h, uint64_t step, void *s)

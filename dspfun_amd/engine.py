@@ -222,10 +222,43 @@ class Plan:
         self._check(self._lib.dspfft_execute_roundtrip_u8_topn(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
                                                                fpp, int(coeff_limit), wp, wb, C.c_void_p(d_coded or None), C.c_void_p(stream)))
 
-    def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0):
-        """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
-        Floyd-Steinberg dithered store of them (pel = value * scalefactor * normalization * normalization), plane by plane over inv's extents"""
+    def _coeff_limit(self, inv, coeff_limit, outside_mul, topn_work):
+        """dspfft_coeff_limit for a call (and what keeps its work buffer alive)"""
+        wp, wb, hold = self._topn_work(inv, topn_work)
+        cl = _lib.CoeffLimit()
+        cl.keep = int(coeff_limit); cl.outside_mul = float(outside_mul); cl.d_work = wp.value if wp is not None else None; cl.work_bytes = wb
+        return cl, hold
+
+    def roundtrip_limit(self, inv, d_in, d_out=None, coeff_limit=0, outside_mul=1.0, filter=None, d_coded=0, stream=0, topn_work=None):
+        """roundtrip with motion --coeff-limit through dspfft_execute_roundtrip_limit: every pair roundtrip(coeff_limit=...) takes, the same
+        bytes, and a rescaled block grid (motion_grid_plans; outside_mul = info["limit_outside_mul"]), whose selection ranks the whole
+        max(block, scaled) embedding as the reference does.  coeff_limit must be at least 1."""
+        d_out = d_in if d_out is None else d_out
         fp = self._filter_params(filter)
+        cl, _hold = self._coeff_limit(inv, coeff_limit, outside_mul, topn_work)
+        self._check(self._lib.dspfft_execute_roundtrip_limit(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), C.byref(fp) if fp is not None else None,
+                                                             C.byref(cl), C.c_void_p(d_coded or None), C.c_void_p(stream)))
+
+    def roundtrip_u8_limit(self, inv, d_in_u8, d_out_u8, d_work, out_mul, coeff_limit=0, outside_mul=1.0, filter=None, d_coded=0, stream=0, topn_work=None):
+        """roundtrip_u8 with motion --coeff-limit through dspfft_execute_roundtrip_u8_limit (see roundtrip_limit); d_work may be None / 0 for
+        a rescaled block grid"""
+        fp = self._filter_params(filter)
+        cl, _hold = self._coeff_limit(inv, coeff_limit, outside_mul, topn_work)
+        self._check(self._lib.dspfft_execute_roundtrip_u8_limit(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
+                                                                C.byref(fp) if fp is not None else None, C.byref(cl), C.c_void_p(d_coded or None), C.c_void_p(stream)))
+
+    def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0,
+                            coeff_limit=0, outside_mul=1.0, topn_work=None):
+        """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
+        Floyd-Steinberg dithered store of them (pel = value * scalefactor * normalization * normalization), plane by plane over inv's extents.
+        coeff_limit (0: none), outside_mul, topn_work: motion --coeff-limit as roundtrip_limit's (dspfft_execute_roundtrip_u8_dither_limit)"""
+        fp = self._filter_params(filter)
+        if coeff_limit:
+            cl, _hold = self._coeff_limit(inv, coeff_limit, outside_mul, topn_work)
+            self._check(self._lib.dspfft_execute_roundtrip_u8_dither_limit(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work),
+                                                                           float(scalefactor), float(normalization), C.byref(fp) if fp is not None else None,
+                                                                           C.byref(cl), C.c_void_p(d_coded or None), C.c_void_p(stream)))
+            return
         self._check(self._lib.dspfft_execute_roundtrip_u8_dither(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work),
                                                                  float(scalefactor), float(normalization), C.byref(fp) if fp is not None else None,
                                                                  C.c_void_p(d_coded or None), C.c_void_p(stream)))
@@ -298,7 +331,8 @@ def motion_grid_plans(shape_dhw, block, scaled, lib=None):
     the far ends is cropped, as the reference crops -- and inv cuts the dense output volume info["out_shape"] into as many blocks of
     `scaled`.  Both carry motion's scales (2 sqrt 2 and its inverse, the per-axis index-0 factors of the uniform range, :644-647,748-751;
     for 2-D blocks the unit axis of the reference's 3-D plans is folded into them).  info: in_shape (the cropped input extents), out_shape,
-    nblocks, active = min(block, scaled) for the filter, scalefactor, normalization, out_mul = scalefactor normalization^2 (roundtrip_u8's)."""
+    nblocks, active = min(block, scaled) for the filter, scalefactor, normalization, out_mul = scalefactor normalization^2 (roundtrip_u8's),
+    limit_outside_mul = roundtrip_limit's outside_mul for these plans (1 for 3-D blocks, 2 for 2-D blocks: the folded unit axis)."""
     import math
     D, H, W = (int(v) for v in shape_dhw)
     (bd, bh, bw), (sd, sh, sw) = (tuple(int(v) for v in t) for t in (block, scaled))
@@ -329,7 +363,7 @@ def motion_grid_plans(shape_dhw, block, scaled, lib=None):
     scalefactor, normalization = ns / nbk, 1.0 / math.sqrt(ns * 8)
     info = dict(in_shape=(nd * bd, nh * bh, nw * bw), out_shape=(Do, Ho, Wo), nblocks=(nd, nh, nw),
                 active=(min(bd, sd), min(bh, sh), min(bw, sw)), scalefactor=scalefactor, normalization=normalization,
-                out_mul=scalefactor * normalization * normalization)
+                out_mul=scalefactor * normalization * normalization, limit_outside_mul=2.0 if two_d else 1.0)
     return fwd, inv, info
 
 

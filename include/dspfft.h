@@ -277,8 +277,9 @@ int dspfft_execute_roundtrip(dspfft_plan fwd, dspfft_plan inv, const float *d_in
  *               the output volume block by block -- the composition the block == scaled path uses
  *   dspfft_plan_set_u8_trc is honoured at both 8-bit ends, the dithered store included
  *   _topn       a keep in range is refused (-2, nothing launched): the reference selects over the whole embedding, forward coefficients
- *               outside min(block, scaled) included (motion.c:652-668), which needs a selection stage of its own -- a follow-up;
+ *               outside min(block, scaled) included (motion.c:652-668), and these entries carry no factor to rank those with;
  *               keep == 0 or keep >= the embedding's count max(block, scaled) is the plain call
+ *   _limit      the forms that take such a keep (dspfft_coeff_limit, below): one kernel of their own, block_rescale_topn.hip
  * -2, with the reason and nothing launched, also for misaligned buffers and for a pair that is almost a grid (different block counts, 2-D
  * against 3-D blocks, an extent outside the list); -3 from a library built without the HIP kernel.  A pair with block == scaled is the
  * path described above: the same kernels, the same bytes. */
@@ -343,13 +344,39 @@ int dspfft_plan_set_u8_trc(dspfft_plan plan, int trc);
  *     filter, the inverse passes.  For this call there is then NO fused column roundtrip and the clip does NOT run in slices: the
  *     selection needs every coefficient of a block before the filter sees one.  d_topn_work holds dspfft_roundtrip_topn_work_bytes.
  * Blocks that are no contiguous runs (interleaved batches; a volume's blocks on misaligned buffers) are refused (-2), and a library built
- * without the HIP selection kernels returns -3 for a keep in range, in both cases with nothing launched.  There is no dithered variant. */
+ * without the HIP selection kernels returns -3 for a keep in range, in both cases with nothing launched.  The dithered variant is dspfft_execute_roundtrip_u8_dither_limit (below). */
 size_t dspfft_roundtrip_topn_work_bytes(dspfft_plan fwd, dspfft_plan inv);
 int dspfft_execute_roundtrip_topn(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const dspfft_motion_filter_params *filter,
                                   size_t keep, void *d_topn_work, size_t work_bytes, unsigned long long *d_coeffs_coded, void *hip_stream);
 int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
                                      const dspfft_motion_filter_params *filter, size_t keep, void *d_topn_work, size_t work_bytes,
                                      unsigned long long *d_coeffs_coded, void *hip_stream);
+
+/* The coefficient limit as one argument, for the calls the two entries above do not cover: a rescaled block grid, and the dithered store.
+ *   keep, d_work, work_bytes   the _topn entries' keep, d_topn_work and work_bytes (a grid needs no work buffer)
+ *   outside_mul                read on a rescaled block grid only.  There the reference multiplies just the A = min(block, scaled) corner of
+ *                              the M = max(block, scaled) embedding by the uniform-range factors (motion.c:644-647) and then ranks EVERY element
+ *                              of the embedding (:652-668).  So, in the order e = (z MY + y) MX + x, an element ranks with: 0 outside `block`;
+ *                              inside A the coefficient as `fwd` writes it (global scale and index-0 factors included); inside `block` but outside A
+ *                              the coefficient WITHOUT `fwd`'s global scale and index-0 factors, times outside_mul.  1 for plans over the
+ *                              reference's own three axes; 2 for the 2-D plans of a depth-1 grid, whose scale has absorbed the reference's unit
+ *                              z axis (REDFT10 over one sample doubles).  A kept coefficient outside A only takes a slot: nothing reads it.
+ * Key, ties, preserve_dc = dc and NaNs are the _topn entries' rules.  On the pairs those entries take, dspfft_execute_roundtrip_limit and
+ * _u8_limit run the same path and give the same bytes.  On a grid pair all three run block_rescale_topn.hip's kernel -- the grid kernel with
+ * unpruned forward passes and the selection in its LDS tile -- and keep >= MX MY MZ is the plain grid call.  _u8_dither_limit takes every pair
+ * dspfft_execute_roundtrip_u8_dither takes (a clip is then not walked in slices) and equals the float-output limit call into d_work followed by
+ * dspfft_motion_dither_u8 over it, byte for byte.
+ * -1, nothing launched: cl NULL, keep == 0 (use the entries without a limit), outside_mul not finite or not > 0, and what the entries
+ * above refuse; -2 / -3 as above. */
+typedef struct { size_t keep; double outside_mul; void *d_work; size_t work_bytes; } dspfft_coeff_limit;
+int dspfft_execute_roundtrip_limit(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const dspfft_motion_filter_params *filter,
+                                   const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_execute_roundtrip_u8_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
+                                      const dspfft_motion_filter_params *filter, const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded,
+                                      void *hip_stream);
+int dspfft_execute_roundtrip_u8_dither_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
+                                             double scalefactor, double normalization, const dspfft_motion_filter_params *filter,
+                                             const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *hip_stream);
 
 /* motion --spectrogram and --ispectrogram (motion/motion.c:617-776 with `spec` / `ispec` set) as one call per clip: the two halves of
  * the roundtrip above, each with ONE plan.
