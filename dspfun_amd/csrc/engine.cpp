@@ -30,6 +30,7 @@
 #include "topn_core.h"
 #include "block_rt.h"
 #include "block_rs_core.h"
+#include "temporal_core.h"
 #include "block_spec_core.h"
 #include "trc_u8_core.h"
 #include "spec_image_core.h"
@@ -69,6 +70,8 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_trc_laun
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_launch(const dspfft::BlockRsArgs *a, int nwg, size_t lds, void *stream);
 // block_rescale_topn.hip's launcher behind the same with a coefficient limit (dspfft_execute_roundtrip_limit and its kin).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_topn_launch(const dspfft::BlockRsTopnArgs *a, int nwg, size_t lds, void *stream);
+// temporal_rt.hip's launcher behind a roundtrip over blocks along time (motion -b 1x1xD).  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_temporal_rt_launch(const dspfft::TemporalArgs *a, int nwg, void *stream);
 // block_spec.hip's and motion_ops.hip's launchers behind dspfft_execute_spectrogram_* / _ispectrogram_*.  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_spec_launch(const dspfft::BlockSpecArgs *a, int inverse, int nwg, size_t lds, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_blocks_launch(int inverse, int u8, void *d_pix, void *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks,
@@ -301,6 +304,9 @@ struct dspfft_plan_s {
 		}
 	};
 	std::vector<std::unique_ptr<RtSlices>> rt_slices;
+	// a roundtrip over blocks along time (rt_temporal): this plan's axis as a complex FFT of its full length with the column pass's tables
+	// (the plan's own pass has none when it is a TINY or DENSE pass), built on first use under rt_mutex
+	std::unique_ptr<Pass> temporal;
 	std::mutex rt_mutex;                     // two host threads may run the same plan pair on their own buffers and streams: the slice plans are made once, and
 	                                         // a call's fork / slices / join are enqueued as one piece (the library stream and its two events are shared)
 	// what plan_finish made this plan under: the planning effort and the planner's switches (EnvScope); its slice plans are made under the same
@@ -1816,6 +1822,9 @@ struct RtCall {
 	BlockRsArgs rs;                       // its arguments, with the geometry derived for the pair
 	int rs_nwg; size_t rs_lds;
 	size_t rs_keep;                       // ... and its coefficient limit (0: none; block_rescale_topn.hip's kernel otherwise)
+	bool temporal;                        // blocks along time that the plans' own passes cannot run (rt_temporal): temporal_rt.hip's kernel runs the call
+	TemporalArgs tp;                      // its arguments but the tables (rt_run_temporal)
+	int tp_nwg;
 };
 // the conversions at the ends of the unfused paths, plain or through the call's transfer characteristic
 int rt_u8_in(const RtCall &c, float *dst, uint64_t len)
@@ -1941,6 +1950,119 @@ int rt_run_grid(const RtCall &c)
 	return 0;
 }
 
+// ---- blocks along time: motion -b 1x1xD, with -s 1x1xD' (motion/README.md:87-89) ----
+// A pair is temporal when both plans are f32 and rank 1, REDFT10 / REDFT01, the transformed axis has stride P > 1 on both sides of both
+// plans, a unit-stride batch dimension holds exactly the P samples of a frame, and at most one further batch dimension, the blocks, lies
+// n P apart (n the plan's own length: fwd over the input clip, inv over the dense output clip), counted alike by both plans.
+struct TemporalPair { int D, S, P, nd; };
+bool rt_temporal_side(const dspfft_plan_s *pl, int kind, int &n, long long &P, long long &nd)
+{
+	if (pl->f64 || pl->rank != 1 || pl->kinds[0] != kind) return false;
+	const Dim &ax = pl->axes[0];
+	n = pl->n[0]; P = ax.is; nd = 1;
+	if (n < 2 || ax.is != ax.os || P <= 1) return false;
+	bool pixels = false, blocks = false;
+	for (const Dim &b : pl->batches) {
+		if (b.n == 1) continue;
+		if (b.is != b.os) return false;
+		if (!pixels && b.is == 1 && b.n == P) pixels = true;
+		else if (!blocks && b.is == (long long)n * P) { blocks = true; nd = b.n; }
+		else return false;
+	}
+	return pixels;
+}
+bool rt_temporal_pair(const dspfft_plan_s *fwd, const dspfft_plan_s *inv, TemporalPair &t)
+{
+	long long Pf, Pi, nf, ni;
+	if (!rt_temporal_side(fwd, DSPFFT_REDFT10, t.D, Pf, nf) || !rt_temporal_side(inv, DSPFFT_REDFT01, t.S, Pi, ni) || Pf != Pi || nf != ni || Pf > 0x7fffffffLL) return false;
+	t.P = (int)Pf; t.nd = (int)nf;
+	return true;
+}
+// does the axis of length n factor into the column pass's radices (no prime factor above 13: no Bluestein)?
+bool temporal_length_ok(int n)
+{
+	for (int p : {2, 3, 5, 7, 11, 13}) while (n % p == 0) n /= p;
+	return n == 1;
+}
+// DSPFFT_TEMPORAL_K=16|32|64|128: a narrower tile than the budget allows (measurements; read on every call)
+int temporal_forced_k()
+{
+	const char *e = getenv("DSPFFT_TEMPORAL_K");
+	const int k = e ? atoi(e) : 0;
+	return (k == 16 || k == 32 || k == 64 || k == 128) ? k : 0;
+}
+
+// 0: the pair is not temporal, or the call is one the plans' own passes run as they always did (float, equal extents, no filter or a
+// pure quantiser); 1: temporal_rt.hip's kernel runs it -- every 8-bit call, every call with D' != D, every float call whose filter needs
+// positions (the stand-alone filter would derive them from a block-major offset) -- c.temporal and c.tp are set and everything about the
+// call is checked; < 0: such a call that cannot run.  Nothing is launched and no table is built here.
+int rt_temporal(RtCall &c)
+{
+	TemporalPair t;
+	if (!rt_temporal_pair(c.fwd, c.inv, t)) return 0;
+	if (int rc = rt_filter(c)) return rc;
+	const bool u8 = c.d_in8 || c.d_out8, positional = c.fp && !c.mf.quant_only;
+	if (c.dithered || (!u8 && t.D == t.S && !positional)) return 0;      // (roundtrip_dither sends a temporal pair's call here as the plain 8-bit one)
+	const char *const what = "roundtrip over blocks along time (motion -b 1x1xD)";
+	const int m = std::max(t.D, t.S);
+	if (c.keep && c.keep < (size_t)m) return fail(-2, "%s: a coefficient limit is not implemented here", what);
+	c.keep = 0;
+	if (!temporal_length_ok(t.D) || !temporal_length_ok(t.S))
+		return fail(-2, "%s: lengths %d and %d must have no prime factor above 13 (the fused kernel has no Bluestein pass)", what, t.D, t.S);
+	int K = temporal_tile_k(m);
+	if (!K) return fail(-2, "%s: max(D, D') = %d is too long for the narrowest tile (16 columns in %d KB of LDS: up to %d)", what, m, TEMPORAL_TILE_BYTES / 1024, TEMPORAL_TILE_BYTES / 64);
+	if (t.P % 4) return fail(-2, "%s: the samples per frame (the frame pitch), %d, must be a multiple of 4", what, t.P);
+	if (!rt_ends_aligned(c)) return fail(-2, "%s: float buffers must be 16-byte aligned, 8-bit buffers 4-byte aligned", what);
+	if (const int fk = temporal_forced_k()) K = std::min(K, fk);
+	const long long ntiles = ((long long)t.P + K - 1) / K, nwg = ntiles * t.nd;
+	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many workgroups for one launch (%lld tiles of %d columns)", what, nwg, K);
+	if (!dspfft_temporal_rt_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, temporal_rt.hip)", what);
+	rt_trc_ends(c);
+	TemporalArgs &a = c.tp;
+	memset((void *)&a, 0, sizeof a);
+	a.D = t.D; a.S = t.S; a.K = K; a.B = K / 2; a.P = t.P; a.ntiles = (int)ntiles;
+	a.blk_in = (long long)t.D * t.P; a.blk_out = (long long)t.S * t.P;
+	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
+	a.f_scale = (float)c.fwd->scale; a.f_in0 = (float)c.fwd->in0[0]; a.f_out0 = (float)c.fwd->out0[0];
+	a.i_scale = (float)c.inv->scale; a.i_in0 = (float)c.inv->in0[0]; a.i_out0 = (float)c.inv->out0[0];
+	a.filt = c.mf; a.coded = c.coded;
+	a.tab_in = (const TrcU8Tab *)c.trc_in.tab; a.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; a.trc_out = c.trc_out.id;
+	a.divB = make_div((uint32_t)a.B); a.divQ = make_div((uint32_t)(K / 4)); a.div_tiles = make_div((uint32_t)a.ntiles);
+	c.tp_nwg = (int)nwg;
+	c.temporal = true;
+	return 1;
+}
+
+// a plan's axis as the column pass sees it: the complex FFT of its full length and the tables T, W, pos (the plan's own pass is a TINY
+// pass without tables up to 32 points)
+int temporal_tables(dspfft_plan_s *pl)
+{
+	std::lock_guard<std::mutex> lock(pl->rt_mutex);
+	if (pl->temporal) return 0;
+	auto P = std::make_unique<Pass>();
+	memset(&P->pa, 0, sizeof P->pa);
+	std::vector<uint32_t> pos;
+	if (!build_fft(pl->n[0], P->pa.fft, pos)) return fail(-2, "roundtrip over blocks along time: length %d does not factor", pl->n[0]);
+	if (upload_tables(*P, false, pl->n[0], pl->n[0], pos)) { P->tab.release(); return fail(-3, "table upload failed"); }
+	pl->temporal = std::move(P);
+	return 0;
+}
+
+// blocks along time: load, forward over D, filter by z, inverse over D', store -- one launch from the forward plan's input clip into the
+// inverse plan's output clip (the same clip for equal extents in place: a tile reads all its frames before it writes any)
+int rt_run_temporal(const RtCall &c)
+{
+	if (int rc = temporal_tables(c.fwd)) return rc;
+	if (int rc = temporal_tables(c.inv)) return rc;
+	TemporalArgs a = c.tp;
+	const Pass &F = *c.fwd->temporal, &I = *c.inv->temporal;
+	a.ff = F.pa.fft; a.fi = I.pa.fft;
+	a.Tf = (const cx<float> *)F.tab.T; a.Wf = (const cx<float> *)F.tab.W; a.posf = (const uint32_t *)F.tab.pos;
+	a.Ti = (const cx<float> *)I.tab.T; a.Wi = (const cx<float> *)I.tab.W; a.posi = (const uint32_t *)I.tab.pos;
+	if (int rc = dspfft_temporal_rt_launch(&a, c.tp_nwg, c.stream)) return fail(-4, "kernel launch failed (blocks along time): backend code %d", rc);
+	return 0;
+}
+
 // every rejection of a roundtrip call; nothing has been launched when it returns
 int rt_check(RtCall &c)
 {
@@ -1948,8 +2070,9 @@ int rt_check(RtCall &c)
 	const dspfft_motion_filter_params *fp = c.fp;
 	if (!fwd || !inv || !(c.d_in || c.d_in8) || !(c.d_out || c.d_out8)) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
+	if (int t = rt_temporal(c)) return t < 0 ? t : 0;          // (ahead of rt_grid, which answers every rescaled pair with batches that it is no grid)
 	if (int g = rt_grid(c)) return g < 0 ? g : 0;
-	if (!c.d_out) return fail(-1, "null plan or buffer");       // (only a rescaled block grid stores its bytes without a float work buffer)
+	if (!c.d_out) return fail(-1, "null plan or buffer");       // (only a rescaled block grid and blocks along time store their bytes without a float work buffer)
 	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
 	const Pass &F = *(c.F = &fwd->passes[nf - 1]), &I = *(c.I = &inv->passes[0]);
 	bool differs = fwd->rank != inv->rank;
@@ -2302,6 +2425,7 @@ int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
 	if (c.grid) rc = rt_run_grid(c);
+	else if (c.temporal) rc = rt_run_temporal(c);
 	else if (c.block) rc = rt_run_block(c);
 	else if (c.rescale) rc = rt_run_rescale(c);
 	else {
@@ -2585,7 +2709,16 @@ namespace {
 int roundtrip_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double scalefactor, double normalization,
                      const dspfft_motion_filter_params *fp, const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
 {
-	if (!fwd || !inv || !d_in || !d_out || !d_work) return fail(-1, "null plan or buffer");
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "null plan or buffer");
+	// blocks along time: a 1 x 1 plane has no neighbour to diffuse into (the conditions of motion.c:781-785 are all false), so the bytes
+	// are the plain 8-bit call's with out_mul = scalefactor normalization^2 -- and that call needs no work buffer
+	TemporalPair tp;
+	if (rt_temporal_pair(fwd, inv, tp)) {
+		if (!(scalefactor > 0) || !(normalization > 0)) return fail(-1, "dither: scalefactor and normalization must be > 0");
+		return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, scalefactor * normalization * normalization, fp, d_coeffs_coded, stream, true, nullptr,
+		                      cl ? cl->keep : 0, cl ? cl->d_work : nullptr, cl ? cl->work_bytes : 0, cl ? cl->outside_mul : 0.0);
+	}
+	if (!d_work) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the dithered roundtrip takes f32 plans");
 	if (!dspfft_dither_launch) return fail(-3, "dithered 8-bit store: not in this build (the dither kernel is HIP-only, motion_dither.hip)");
 	if (!(scalefactor > 0) || !(normalization > 0)) return fail(-1, "dither: scalefactor and normalization must be > 0");
@@ -2705,7 +2838,7 @@ static bool many_pair_check(const dspfft_plan *plans, const void *const *d_in, v
 	c = RtCall{fwd, inv, (const float *)d_in[i], (float *)d_out[i], nullptr, nullptr, 1.0, nullptr, nullptr, streams ? streams[i] : nullptr, 0, nullptr, 0};
 	char err[sizeof g_err];
 	memcpy(err, g_err, sizeof err);                  // a pair that is none is no error of the batch
-	const bool ok = rt_check(c) == 0 && !c.grid && !c.block && !c.rescale;
+	const bool ok = rt_check(c) == 0 && !c.grid && !c.temporal && !c.block && !c.rescale;
 	memcpy(g_err, err, sizeof err);
 	if (!ok) return false;
 	PassArgs af, ai;
@@ -2837,6 +2970,7 @@ extern "C" void dspfft_destroy_plan(dspfft_plan pl)
 	if (!pl) return;
 	for (Pass &P : pl->passes) P.tab.release();
 	for (Pass &P : pl->split) P.tab.release();
+	if (pl->temporal) pl->temporal->tab.release();
 	be_free(pl->zflags); be_free(pl->zpage); be_free(pl->zranges); be_free(pl->eids);
 	if (pl->u8_tab_owned) be_free(pl->u8_tab);
 	delete pl;

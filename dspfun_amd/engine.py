@@ -211,7 +211,8 @@ class Plan:
         """the same with motion's 8-bit samples at both ends (motion.c:617-640, :760-776): u8 in, float work buffer, u8 out =
         quantise(value * out_mul); the conversions ride on the first and last row passes when those are planar specialised passes.
         coeff_limit, topn_work: as roundtrip's (dspfft_execute_roundtrip_u8_topn).  d_work may be None / 0 for a rescaled block grid
-        (motion_grid_plans: one kernel from the input volume to the output volume, no float intermediate); every other pair needs it."""
+        (motion_grid_plans: one kernel from the input volume to the output volume, no float intermediate) and for blocks along time
+        (motion_temporal_plans, likewise); every other pair needs it."""
         fp = self._filter_params(filter)
         fpp = C.byref(fp) if fp is not None else None
         if not coeff_limit:
@@ -364,6 +365,40 @@ def motion_grid_plans(shape_dhw, block, scaled, lib=None):
     info = dict(in_shape=(nd * bd, nh * bh, nw * bw), out_shape=(Do, Ho, Wo), nblocks=(nd, nh, nw),
                 active=(min(bd, sd), min(bh, sh), min(bw, sw)), scalefactor=scalefactor, normalization=normalization,
                 out_mul=scalefactor * normalization * normalization, limit_outside_mul=2.0 if two_d else 1.0)
+    return fwd, inv, info
+
+
+def motion_temporal_plans(shape_dhw, block_d, scaled_d=None, lib=None):
+    """motion --blocksize 1x1xD (--size 1x1xD') over a [D_total][H][W] plane (motion/README.md:87-89, motion/motion.c:488-499,535-552,
+    566-567): every pixel of every run of D = block_d frames is a 1-D block, transformed over D, filtered by z and transformed back over
+    D' = scaled_d (default D).  The plan pair of dspfft_execute_roundtrip*: fwd is a rank-1 REDFT10 of length D along the frame axis, at
+    stride P = H W, batched over the nd = D_total // D blocks and the P pixels (P a multiple of 4; leftover frames are cropped, as the
+    reference crops them); inv the REDFT01 of length D' over the dense output clip [nd D'][H][W].  Both carry motion's scales with the two
+    unit axes of the reference's 3-D plans folded in, sqrt 2 each (:644-647,748-751).  info: in_shape (the cropped input), out_shape,
+    nblocks, active = (min(D, D'), 1, 1), scalefactor = D' / D, normalization = 1 / sqrt(8 D'), out_mul = scalefactor normalization^2
+    (roundtrip_u8's).  Filter dictionaries for these plans: active = info["active"], minbuf_hw = (1, 1), block_depth = max(D, D'), bands
+    (z0, 0, 0) to (z1, 1, 1).  The 8-bit call runs in place for D' = D; with D' != D input and output must not overlap."""
+    import math
+    Dt, H, W = (int(v) for v in shape_dhw)
+    D = int(block_d)
+    S = D if scaled_d is None else int(scaled_d)
+    P = H * W
+    if D < 2 or S < 2:
+        raise ValueError("block_d and scaled_d must be at least 2")
+    if P < 4 or P % 4:
+        raise ValueError("the samples per frame H * W must be a multiple of 4")
+    nd = Dt // D
+    if not nd:
+        raise ValueError("the clip holds no whole block")
+    r2 = math.sqrt(2.0)
+    how = lambda n: [(nd, n * P, n * P), (P, 1, 1)]
+    # (a unit axis of the reference's 3-D plans: REDFT10 doubles and the uniform range divides by sqrt 2; the inverse multiplies by sqrt 2)
+    unit = r2
+    fwd = Plan.guru([(D, P, P)], how(D), [REDFT10], lib=lib).set_scale(2 * r2 * unit * unit).set_axis_scale0(0, 1.0, 1.0 / r2)
+    inv = Plan.guru([(S, P, P)], how(S), [REDFT01], lib=lib).set_scale(unit * unit / (2 * r2)).set_axis_scale0(0, r2, 1.0)
+    scalefactor, normalization = S / D, 1.0 / math.sqrt(S * 8.0)
+    info = dict(in_shape=(nd * D, H, W), out_shape=(nd * S, H, W), nblocks=(nd, H, W), active=(min(D, S), 1, 1), scalefactor=scalefactor,
+                normalization=normalization, out_mul=scalefactor * normalization * normalization)
     return fwd, inv, info
 
 

@@ -282,7 +282,26 @@ int dspfft_execute_roundtrip(dspfft_plan fwd, dspfft_plan inv, const float *d_in
  *   _limit      the forms that take such a keep (dspfft_coeff_limit, below): one kernel of their own, block_rescale_topn.hip
  * -2, with the reason and nothing launched, also for misaligned buffers and for a pair that is almost a grid (different block counts, 2-D
  * against 3-D blocks, an extent outside the list); -3 from a library built without the HIP kernel.  A pair with block == scaled is the
- * path described above: the same kernels, the same bytes. */
+ * path described above: the same kernels, the same bytes.
+ *
+ * Blocks ALONG TIME (motion --blocksize 1x1xD, with --size 1x1xD'; motion/README.md:87-89): every pixel of every run of D frames of a
+ * [frames][H][W] plane is a 1-D block.  The pair is such a clip when both plans are f32 and rank 1, `fwd` REDFT10 of length D and `inv`
+ * REDFT01 of length D', the transformed axis at stride P = H W > 1 in place, with a unit-stride batch dimension of exactly P samples and
+ * at most one further batch dimension, the blocks, n P apart (n the plan's own length: `fwd` over the input clip, `inv` over the dense
+ * output clip [blocks D'][H][W]), both plans counting the same blocks and pixels (dspfft_plan_guru_r2r; engine.motion_temporal_plans
+ * makes the pair with motion's scales).  On such a pair ONE kernel (temporal_rt.hip) loads a tile of pixel columns, transforms over D,
+ * filters at (z, 0, 0) for z < min(D, D'), transforms back over D' and stores, touching memory at the two ends only.  It takes
+ *   every _u8 and _u8_dither call   d_work is not touched and may be NULL; a 1 x 1 block has no neighbour to diffuse into (the
+ *                                   conditions of motion.c:781-785 are all false), so the dithered call's bytes are those of the _u8 call
+ *                                   with out_mul = scalefactor normalization^2; dspfft_plan_set_u8_trc is honoured at both 8-bit ends
+ *   every call with D' != D         d_in in `fwd`'s input layout, d_out in `inv`'s output layout; input and output must not overlap
+ *   every float call whose filter needs positions (any filter but a pure quantiser): the stand-alone filter would derive them from a
+ *                                   block-major offset; here positions are the block's own and minbuf_hw / block_depth are not consulted
+ * For D' == D the 8-bit call may run in place (a tile reads all its frames before it writes any).  A float call on equal extents with no
+ * filter or a pure quantiser runs the plans' own passes, as it always did.  -2, with the reason and nothing launched: a coefficient limit
+ * below max(D, D') in any _topn / _limit entry, a length with a prime factor above 13, max(D, D') above 1024 (the narrowest tile of 16
+ * columns in 64 KB of LDS), P no multiple of 4, float buffers off 16 bytes or 8-bit buffers off 4, more than 2^31 - 1 workgroups; -3 from a
+ * library built without the HIP kernel. */
 
 /* The same with motion's 8-bit samples at both ends (motion/motion.c:617-640 load, :760-776 store): d_in and d_out
  * hold uint8 samples in the plans' input / output element layout, d_work is a float buffer in the plans' working
