@@ -41,6 +41,7 @@ SYMBOLS = [
     "dspfft_applybasis_work_floats_ex", "dspfft_applybasis_partsums_ex", "dspfft_applybasis_render",
     "dspfft_motion_load_u8", "dspfft_motion_store_u8", "dspfft_motion_load_f32", "dspfft_motion_store_f32", "dspfft_motion_topn_work_bytes", "dspfft_motion_topn", "dspfft_motion_last_error", "dspfft_motion_dither_u8",
     "dspfft_spec_encode", "dspfft_ispec_decode", "dspfft_ispec_signmap", "dspfft_motion_filter", "dspfft_scan_pruned_accumulate", "dspfft_scan_pruned_work_floats", "dspfft_scan_pruned_accumulate_ws", "dspfft_pointwise_last_error",
+    "dspfft_rotate_parse", "dspfft_rotate",
 ]
 
 class IoDim(C.Structure):
@@ -220,6 +221,9 @@ def bind(lib):
         lib.dspfft_f32_to_u8_trc.argtypes = [vp, vp, C.c_double, C.c_uint64, C.c_int, vp]
         lib.dspfft_motion_load_u8_linear.argtypes = [vp, vp, ip, ip, C.c_int, vp]
         lib.dspfft_motion_store_u8_linear.argtypes = [vp, vp, ip, ip, C.c_double, C.c_double, C.c_int, vp]
+    if hasattr(lib, "dspfft_rotate"):            # (likewise; the CPU emulation used in tests has none either)
+        lib.dspfft_rotate_parse.argtypes = [C.c_char_p, ip, ip]
+        lib.dspfft_rotate.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_int, ip, ip, vp]
     if hasattr(lib, "dspfft_zoom_product"):      # HIP-only entry points (absent from the CPU emulation used in tests)
         lib.dspfft_zoom_ncomponents.restype = C.c_size_t
         lib.dspfft_zoom_ncomponents.argtypes = [C.c_double, C.c_double, C.c_size_t]

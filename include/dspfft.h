@@ -718,6 +718,22 @@ int dspfft_motion_topn_blocks(float *d_coeffs, size_t count, size_t nblocks, lon
                               void *hip_stream);
 const char *dspfft_motion_last_error(void);
 
+/* ---- rotate (motion/rotate.c): a clip's three axes permuted, with flips ---- */
+
+/* rotate.c:74-89 on `spec` ("zyx", "-yx+z", ...), host only: at position p a '-' sets invert[p] and a '+' is skipped, each before the letter
+ * of its own position, and the letter gives map[p] = letter - 'x'; what follows the third letter is not read.  Non-zero for a string the
+ * reference sends to usage() and, beyond the reference, for a map that is no permutation ("xxy"). */
+int dspfft_rotate_parse(const char *spec, int map[3], int invert[3]);
+/* rotate.c:159-164 on a dense device clip d_in[len[2]][len[1]][len[0]] of elements of elem_bytes = 1 (a planar 8-bit plane), 2, 3 (rgb24),
+ * 4 (rgba, or a planar float plane): output axis o (0 = x) runs over input axis map[o], so d_out is [len[map[2]]][len[map[1]]][len[map[0]]],
+ * and input axis a is read backwards iff invert[map[a]] -- for the two 3-cycles not the axis the signed letter names ("-yzx" flips input z),
+ * as the reference.  Stream-ordered, no allocation, no host synchronisation; all offsets 64-bit.  The base pointers need only be aligned to
+ * the element (2 and 4 bytes: to that many; 1 and 3: any address), so -s start:nframes is d_in + start len[0] len[1] elem_bytes and a
+ * smaller len[2].  Non-zero, with the reason in dspfft_motion_last_error() and nothing launched: a zero extent, elem_bytes outside 1..4, a
+ * map that is no permutation, a null or misaligned pointer, overlapping input and output (there is no in-place form), more than 2^31 - 1
+ * tiles. */
+int dspfft_rotate(void *d_out, const void *d_in, const uint64_t len[3], int elem_bytes, const int map[3], const int invert[3], void *hip_stream);
+
 /* scan/scan.c:451-459 arithmetic: sum += image (len floats). */
 int dspfft_accumulate(float *d_sum, const float *d_image, uint64_t len, void *hip_stream);
 
