@@ -22,6 +22,7 @@ SYMBOLS = [
     "dspfft_motion_spec_blocks_u8", "dspfft_motion_spec_blocks_f32", "dspfft_motion_ispec_blocks_u8", "dspfft_motion_ispec_blocks_f32",
     "dspfft_roundtrip_topn_work_bytes", "dspfft_execute_roundtrip_topn", "dspfft_execute_roundtrip_u8_topn", "dspfft_motion_topn_blocks_work_bytes", "dspfft_motion_topn_blocks",
     "dspfft_execute_roundtrip_limit", "dspfft_execute_roundtrip_u8_limit", "dspfft_execute_roundtrip_u8_dither_limit",
+    "dspfft_execute_roundtrip_u8_packed",
     "dspfft_execute","dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
     "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_many_fused_pairs", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_execute_n", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
     "dspfft_last_error", "dspfft_version", "dspfft_set_thread_plan_effort", "dspfft_get_thread_plan_effort", "dspfft_fftw_sparse_uploads",
@@ -57,6 +58,11 @@ class DitherGeom(C.Structure):
 class CoeffLimit(C.Structure):
     """dspfft_coeff_limit (include/dspfft.h)"""
     _fields_ = [("keep", C.c_size_t), ("outside_mul", C.c_double), ("d_work", C.c_void_p), ("work_bytes", C.c_size_t)]
+
+
+class MotionPacked(C.Structure):
+    """dspfft_motion_packed (include/dspfft.h)"""
+    _fields_ = [("components", C.c_int), ("damp", C.c_float * 4), ("boost", C.c_float * 4), ("grey_add", C.c_float * 4)]
 
 
 class ScanFrameOpts(C.Structure):
@@ -147,6 +153,8 @@ def bind(lib):
         lib.dspfft_execute_roundtrip_limit.argtypes = [vp, vp, vp, vp, C.POINTER(MotionFilterParams), C.POINTER(CoeffLimit), vp, vp]
         lib.dspfft_execute_roundtrip_u8_limit.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(CoeffLimit), vp, vp]
         lib.dspfft_execute_roundtrip_u8_dither_limit.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(CoeffLimit), vp, vp]
+    if hasattr(lib, "dspfft_execute_roundtrip_u8_packed"):    # (as above)
+        lib.dspfft_execute_roundtrip_u8_packed.argtypes = [vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(MotionPacked), C.POINTER(CoeffLimit), vp, vp]
     if hasattr(lib, "dspfft_execute_spectrogram_u8"):     # (likewise)
         spp, fpp = C.POINTER(MotionSpecParams), C.POINTER(MotionFilterParams)
         lib.dspfft_execute_spectrogram_u8.argtypes = lib.dspfft_execute_spectrogram_f32.argtypes = [vp, vp, vp, vp, spp, fpp, vp, vp]

@@ -30,6 +30,7 @@
 #include "topn_core.h"
 #include "block_rt.h"
 #include "block_rs_core.h"
+#include "block_packed_core.h"
 #include "temporal_core.h"
 #include "block_spec_core.h"
 #include "trc_u8_core.h"
@@ -70,6 +71,8 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_trc_laun
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_launch(const dspfft::BlockRsArgs *a, int nwg, size_t lds, void *stream);
 // block_rescale_topn.hip's launcher behind the same with a coefficient limit (dspfft_execute_roundtrip_limit and its kin).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_topn_launch(const dspfft::BlockRsTopnArgs *a, int nwg, size_t lds, void *stream);
+// block_packed.hip's launcher behind dspfft_execute_roundtrip_u8_packed (packed 8-bit pixels through the fused block roundtrip).  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_packed_launch(const dspfft::BlockPackedArgs *a, int nwg, size_t lds, void *stream);
 // temporal_rt.hip's launcher behind a roundtrip over blocks along time (motion -b 1x1xD).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_temporal_rt_launch(const dspfft::TemporalArgs *a, int nwg, void *stream);
 // block_spec.hip's and motion_ops.hip's launchers behind dspfft_execute_spectrogram_* / _ispectrogram_*.  Weak, as above.
@@ -2767,6 +2770,62 @@ extern "C" int dspfft_execute_roundtrip_u8_dither_limit(dspfft_plan fwd, dspfft_
 {
 	if (int rc = coeff_limit_check(cl)) return rc;
 	return roundtrip_dither(fwd, inv, d_in, d_out, d_work, scalefactor, normalization, fp, cl, d_coeffs_coded, stream);
+}
+
+// motion on packed 8-bit pixels (rgb24, rgba ...; include/dspfft.h): the planar small-block pair's geometry with every stride and offset times
+// `components`, block_packed.hip's kernel.  Every check comes before the launch.
+extern "C" int dspfft_execute_roundtrip_u8_packed(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
+                                                  const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed, const dspfft_coeff_limit *cl,
+                                                  unsigned long long *d_coeffs_coded, void *stream)
+{
+	const char *const what = "roundtrip on packed 8-bit pixels";
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", what);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", what);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", what);
+	if (cl && !cl->keep) return fail(-1, "%s: coefficient limit: keep must be at least 1 (pass NULL for no limit)", what);
+	if (fp && (fp->preserve_dc < 0 || fp->preserve_dc > 2 || fp->minbuf_hw[0] < 1 || fp->minbuf_hw[1] < 1 || fp->block_depth < 1)) return fail(-1, "%s: bad filter parameters", what);
+	const int C = packed->components;
+	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
+	bool differs = fwd->rank != inv->rank;
+	for (int a = 0; !differs && a < fwd->rank; a++) differs = fwd->n[a] != inv->n[a];
+	if (differs && fwd->has_block && inv->has_block) return fail(-2, "%s: different forward / inverse extents (a rescaled block grid, motion -s) are not implemented on packed pixels", what);
+	if (!block_roundtrip_ok(fwd, inv))
+		return fail(-2, "%s needs the plan pair of the fused block pass: matching REDFT10 / REDFT01 small-block plans (every extent 4, 8 or 16, 2-D blocks up to 32; per-frame and single-block plans have no block pass)", what);
+	if (3u & ((uintptr_t)d_in | (uintptr_t)d_out)) return fail(-2, "%s: the buffers must be 4-byte aligned", what);
+	BlockPackedArgs a;
+	memset((void *)&a, 0, sizeof a);
+	static_cast<BlockGeom &>(a) = fwd->blk;
+	const BlockGeom &o = inv->blk;
+	a.sy_out = o.sy_out; a.sz_out = o.sz_out; a.sxb_out = o.sxb_out;
+	for (int d = 0; d < o.nd; d++) a.bos[d] = o.bos[d];
+	// the plans count pixels; the kernel addresses bytes
+	a.sy_in *= C; a.sz_in *= C; a.sxb_in *= C; a.sy_out *= C; a.sz_out *= C; a.sxb_out *= C;
+	long long nwg = 1;
+	for (int d = 0; d < a.nd; d++) { a.bis[d] *= C; a.bos[d] *= C; nwg *= a.bn[d]; }
+	int G = packed_group_of(a.nx, a.ny, a.nz, C, a.nxb);
+	if (const char *e = getenv("DSPFFT_PACKED_G")) { if (atoi(e) > 0) G = std::min(atoi(e), a.nxb); }      // experiments (tools/bench_motion_packed.py)
+	const size_t block_bytes = (size_t)a.nz * a.ny * C * a.nx * sizeof(float);
+	if (block_bytes + sizeof(TrcU8Tab) + 16 > 64 * 1024)
+		return fail(-2, "%s: the %d component tiles of a %dx%dx%d block (%zu bytes) and the tables do not fit a workgroup's 64 KB of LDS", what, C, a.nx, a.ny, a.nz, block_bytes);
+	while (G > 1 && (size_t)G * block_bytes + sizeof(TrcU8Tab) + 16 > 64 * 1024) G--;
+	a.G = G; a.pitch = G * C * a.nx; a.ngroups = (a.nxb + G - 1) / G; a.gdiv = make_div((uint32_t)a.ngroups);
+	nwg *= a.ngroups;
+	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch (more than 2^31 - 1 workgroups)", what);
+	a.in8 = d_in; a.out8 = d_out; a.mul8 = out_mul;
+	block_scales(fwd, a.f); block_scales(inv, a.i);
+	a.comps = C;
+	if (fp) {
+		motion_filter_of(*fp, a.filt);
+		for (int c = 0; c < C; c++) { a.damp[c] = packed->damp[c]; a.boost[c] = packed->boost[c]; a.grey_add[c] = packed->grey_add[c]; }
+		a.coded = d_coeffs_coded;
+	}
+	// --coeff-limit: at or above the block's count nothing is dropped (motion.c:654-657) and the call is the plain one
+	a.keep = cl && cl->keep < (size_t)a.nx * a.ny * a.nz ? (unsigned int)cl->keep : 0;
+	if (fwd->u8_trc) a.tab_in = (const TrcU8Tab *)fwd->u8_tab;
+	if (inv->u8_trc) { a.tab_out = (const TrcU8Tab *)inv->u8_tab; a.trc_out = inv->u8_trc; }
+	if (!dspfft_block_packed_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_packed.hip)", what);
+	if (int rc = dspfft_block_packed_launch(&a, (int)nwg, (size_t)G * block_bytes, stream)) return fail(-4, "kernel launch failed (%s): backend code %d", what, rc);
+	return 0;
 }
 
 extern "C" int dspfft_scan_zigzag_frame_ids(uint32_t *d_ids, uint32_t w, uint32_t h, uint64_t step, void *s)

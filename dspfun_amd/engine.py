@@ -248,6 +248,20 @@ class Plan:
         self._check(self._lib.dspfft_execute_roundtrip_u8_limit(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
                                                                 C.byref(fp) if fp is not None else None, C.byref(cl), C.c_void_p(d_coded or None), C.c_void_p(stream)))
 
+    def roundtrip_u8_packed(self, inv, d_in_u8, d_out_u8, out_mul, packed, filter=None, coeff_limit=0, d_coded=0, stream=0):
+        """dspfft_execute_roundtrip_u8_packed: the fused small-block roundtrip on packed 8-bit pixels (rgb24, rgba ...).  self / inv: the planar
+        small-block pair (motion_grid_plans(shape, block, block)), planned over the clip in pixels; the buffers hold packed.components bytes per
+        pixel.  packed: motion_packed(...) -- its damp, boost and grey_add (by byte position) replace the filter's; filter: as roundtrip_u8's,
+        or None.  coeff_limit: motion --coeff-limit per component block (0: none).  Needs no work buffer; may run in place."""
+        fp = self._filter_params(filter)
+        cl = None
+        if coeff_limit:
+            cl = _lib.CoeffLimit()
+            cl.keep = int(coeff_limit); cl.outside_mul = 1.0; cl.d_work = None; cl.work_bytes = 0
+        self._check(self._lib.dspfft_execute_roundtrip_u8_packed(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
+                                                                 C.byref(fp) if fp is not None else None, C.byref(packed) if packed is not None else None,
+                                                                 C.byref(cl) if cl is not None else None, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+
     def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0,
                             coeff_limit=0, outside_mul=1.0, topn_work=None):
         """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
@@ -366,6 +380,45 @@ def motion_grid_plans(shape_dhw, block, scaled, lib=None):
                 active=(min(bd, sd), min(bh, sh), min(bw, sw)), scalefactor=scalefactor, normalization=normalization,
                 out_mul=scalefactor * normalization * normalization, limit_outside_mul=2.0 if two_d else 1.0)
     return fwd, inv, info
+
+
+#: 8-bit packed pixel formats whose every byte is a component: the byte position of each component, in the reference's component order
+#: (R, G, B[, A] or Y, A), as libavutil's pixel format descriptors place them
+PACKED_FORMATS = {"rgb24": (0, 1, 2), "bgr24": (2, 1, 0), "rgba": (0, 1, 2, 3), "bgra": (2, 1, 0, 3), "argb": (1, 2, 3, 0), "abgr": (3, 2, 1, 0),
+                  "ya8": (0, 1)}
+_PACKED_PADDED = ("rgb0", "bgr0", "0rgb", "0bgr")
+
+
+def motion_packed(pix_fmt, boost=None, damp=None, dcstop=False, normalization=1.0, scalefactor=1.0):
+    """The dspfft_motion_packed of Plan.roundtrip_u8_packed for an 8-bit packed pixel format (PACKED_FORMATS).  boost / damp: motion's -B / -D,
+    up to four values in the reference's component order (r:g:b:a), filled up by its rule (motion/motion.c:235-236: a missing entry repeats the
+    one before it; none at all gives 1 for boost and 0 for damp).  grey_add[i] = (1 - (damp[i] if dcstop else boost[i])) 127.5 /
+    (normalization^2 scalefactor) (:736; dcstop: the pass band does not begin at the origin).  All three are stored by BYTE POSITION.
+    Formats with a byte that is no component (rgb0, 0rgb ...: the reference never writes it), gray (the planar call) and anything that is not
+    8-bit are refused with a ValueError."""
+    fmt = str(pix_fmt)
+    if fmt in _PACKED_PADDED:
+        raise ValueError(f"pixel format {fmt!r} has a padding byte that is no component: not a packed format of roundtrip_u8_packed")
+    if fmt in ("gray", "gray8", "y8"):
+        raise ValueError(f"pixel format {fmt!r} has one component: that is the planar call (roundtrip_u8)")
+    if fmt not in PACKED_FORMATS:
+        raise ValueError(f"pixel format {fmt!r} is not an 8-bit packed format with every byte a component (one of {', '.join(PACKED_FORMATS)})")
+    pos = PACKED_FORMATS[fmt]
+
+    def fill(v, first):
+        v = [] if v is None else ([float(v)] if isinstance(v, (int, float)) else [float(x) for x in v])
+        if len(v) > 4:
+            raise ValueError("at most four values (r:g:b:a)")
+        for i in range(len(v), 4):
+            v.append(v[i - 1] if i else first)
+        return v
+    b, d = fill(boost, 1.0), fill(damp, 0.0)
+    p = _lib.MotionPacked()
+    p.components = len(pos)
+    for i, at in enumerate(pos):
+        p.boost[at], p.damp[at] = b[i], d[i]
+        p.grey_add[at] = (1.0 - (d[i] if dcstop else b[i])) * 127.5 / (float(normalization) ** 2 * float(scalefactor))
+    return p
 
 
 def motion_temporal_plans(shape_dhw, block_d, scaled_d=None, lib=None):

@@ -397,6 +397,39 @@ int dspfft_execute_roundtrip_u8_dither_limit(dspfft_plan fwd, dspfft_plan inv, c
                                              double scalefactor, double normalization, const dspfft_motion_filter_params *filter,
                                              const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *hip_stream);
 
+/* The fused small-block roundtrip on PACKED 8-bit pixels (motion -b 8x8x8 -q 20 -c pixel_format=rgb24, motion/motion.c:155-156: rgb24, bgr24,
+ * rgba, bgra, argb, abgr, ya8): d_in and d_out hold `components` bytes per pixel, every byte a component, and each component of each pixel
+ * block is a block of its own, as in the reference (:613-615) -- for the transform, for --coeff-limit (a selection per component block,
+ * :652-668), for preserve_dc and for d_coeffs_coded, which counts the sum over the components.  ONE kernel (block_packed.hip): a thread reads
+ * the NX * components contiguous bytes of a pixel block's line as whole dwords and picks the components apart in registers, so the clip moves
+ * 2 * components bytes per pixel, where splitting it into planes, one planar call per plane and interleaving again moves about three times that.
+ *   fwd, inv     the PLANAR small-block pair of dspfft_execute_roundtrip_u8's fused block pass (volume layout or block-major), planned over
+ *                the clip in PIXELS; the call multiplies every stride and offset by `components`.  The same pair runs the planar call on a
+ *                de-interleaved plane, and the bytes of this call EQUAL those of the planar call on each component's plane with that
+ *                component's damp, boost and grey_add.
+ *   filter       NULL: none, and only packed->components is read.  Otherwise packed->damp, boost and grey_add, indexed by BYTE POSITION inside
+ *                the pixel, replace filter->damp, filter->boost and filter->grey_add (motion -D / -B r:g:b:a, :235-236,736), which are not
+ *                read; every other field applies to all components (packed formats have no subsampling).
+ *   cl           NULL: no --coeff-limit.  keep == 0 is refused (-1); keep >= the block's count is the plain call, same bytes; outside_mul,
+ *                d_work and work_bytes are not read.
+ *   dspfft_plan_set_u8_trc on either plan is honoured at that end, as in the planar call.
+ * The call may run in place (d_in == d_out: a workgroup reads all its blocks before it writes any), is stream-ordered, allocates nothing and
+ * uses no work buffer.  Nothing is launched when it fails:
+ *   -1  a NULL plan, buffer or `packed`; an f64 plan; cl with keep == 0; bad filter parameters
+ *   -2  components outside 2..4; a pair the fused block pass does not take (per-frame plans, one 3-D block); different extents in fwd and
+ *       inv (a rescaled grid: motion -s is not implemented on packed pixels, nor are -d and --spectrogram / --ispectrogram); buffers off
+ *       4 bytes; a block whose `components` tiles plus the tables do not fit one workgroup's 64 KB of LDS -- of the listed extents that is
+ *       16 x 16 x 16 at four components --; more than 2^31 - 1 workgroups
+ *   -3  a library built without the HIP kernel */
+typedef struct {
+	int   components;                       /* 2, 3 or 4 bytes per pixel, every byte a component */
+	float damp[4], boost[4], grey_add[4];   /* indexed by BYTE POSITION inside the pixel */
+} dspfft_motion_packed;
+int dspfft_execute_roundtrip_u8_packed(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
+                                       const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                       const dspfft_coeff_limit *cl /* NULL: no --coeff-limit */,
+                                       unsigned long long *d_coeffs_coded, void *hip_stream);
+
 /* motion --spectrogram and --ispectrogram (motion/motion.c:617-776 with `spec` / `ispec` set) as one call per clip: the two halves of
  * the roundtrip above, each with ONE plan.
  *   spectrogram   load (:621-625) -> REDFT10 over `fwd`'s extents (`fwd` carries motion's index-0 factors, dspfft_plan_set_axis_scale0,
