@@ -1717,38 +1717,38 @@ bool pass_has_u8(const dspfft_plan_s *pl, const Pass &P, bool rgb = false)
 	return (P.has_spec && be_spec_has_u8(P.spec.id)) || (P.jit && P.jit_fn_u8);
 }
 
-int run_pass_u8(const dspfft_plan_s *pl, const Pass &P, const float *in, float *out, bool last, const U8IO &io, void *stream)
+// motion's -d (dspfft_execute_roundtrip_u8_dither): the bytes come from the dither kernel (motion_dither.hip) instead of the last inverse pass
+struct Dither { uint8_t *out8; double sf, norm; };
+// the transfer characteristic of one 8-bit end of a roundtrip call (id = 0: none) and its tables on the device
+struct U8Trc { int id = 0; const void *tab = nullptr; };
+// A plan's first row pass loading ends.in, or its last row pass storing quantise(value * ends.mul) to ends.out, in place in `work`.  trc.id: through
+// the listed kernel that has that characteristic's table at its 8-bit end (rt_check has seen to it that the pass has a listed kernel and that
+// the launcher is there).
+int run_pass_u8(const dspfft_plan_s *pl, const Pass &P, float *work, const U8IO &ends, const U8Trc &trc, void *stream)
 {
+	const bool last = ends.out != nullptr;
 	PassArgs a;
-	fill_args(a, P.spa, pl, P, in, out, last ? pl->scale : 1.0, Fuse());
+	fill_args(a, P.spa, pl, P, work, work, last ? pl->scale : 1.0, Fuse());
+	if (trc.id) {
+		U8IOTrc io;
+		static_cast<U8IO &>(io) = ends;
+		(last ? io.tab_out : io.tab_in) = (const TrcU8Tab *)trc.tab; io.trc_out = last ? trc.id : 0;
+		if (int rc = dspfft_row_u8_trc_launch(P.spec.id, &a, &io, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8 with a transfer characteristic): backend code %d", P.desc.c_str(), rc);
+		return 0;
+	}
 	if (P.jit && !P.has_spec) {
-		U8IO io2 = io;
+		U8IO io2 = ends;
 		void *args[2] = {&a, &io2};
 		if (int rc = be_jit_launch_n(P.jit_fn_u8, args, P.spec_nwg, P.jit_nthr, stream)) return fail(-4, "kernel launch failed (%s, u8): backend code %d", P.desc.c_str(), rc);
 		return 0;
 	}
 	if (P.pa.C == 3) {        // interleaved RGB lines (pass_has_u8 with rgb)
-		if (int rc = dspfft_row_u8c_launch(P.spec.id, &a, &io, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8 rgb): backend code %d", P.desc.c_str(), rc);
+		if (int rc = dspfft_row_u8c_launch(P.spec.id, &a, &ends, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8 rgb): backend code %d", P.desc.c_str(), rc);
 		return 0;
 	}
-	if (int rc = be_launch_spec_u8(P.spec.id, a, io, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8): backend code %d", P.desc.c_str(), rc);
+	if (int rc = be_launch_spec_u8(P.spec.id, a, ends, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8): backend code %d", P.desc.c_str(), rc);
 	return 0;
 }
-
-// the same pass through the listed kernel that has a transfer characteristic's table at its 8-bit end (rt_check has seen to it that the pass
-// has a listed kernel and that the launcher is there)
-int run_pass_u8_trc(const dspfft_plan_s *pl, const Pass &P, const float *in, float *out, bool last, const U8IOTrc &io, void *stream)
-{
-	PassArgs a;
-	fill_args(a, P.spa, pl, P, in, out, last ? pl->scale : 1.0, Fuse());
-	if (int rc = dspfft_row_u8_trc_launch(P.spec.id, &a, &io, P.spec_nwg, stream)) return fail(-4, "kernel launch failed (%s, u8 with a transfer characteristic): backend code %d", P.desc.c_str(), rc);
-	return 0;
-}
-
-// motion's -d (dspfft_execute_roundtrip_u8_dither): the bytes come from the dither kernel (motion_dither.hip) instead of the last inverse pass
-struct Dither { uint8_t *out8; double sf, norm; };
-// the transfer characteristic of one 8-bit end of a roundtrip call (id = 0: none) and its tables on the device
-struct U8Trc { int id = 0; const void *tab = nullptr; };
 // the planes of a plan's output layout: its last two axes (rank 1: rows of their own), the first of three and the batch axes index planes
 int dither_geom_of(const dspfft_plan_s *p, dspfft_dither_geom &g)
 {
@@ -1776,15 +1776,21 @@ int dither_store(const dspfft_plan_s *inv, const float *work, const Dither &dz, 
 	           : dspfft_dither_launch(dz.out8, work, &g, dz.sf, dz.norm, stream, err, sizeof err)) return fail(-4, "%s", err);
 	return 0;
 }
-int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
-                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice = true,
-                   const Dither *dither = nullptr, size_t keep = 0, void *topn_work = nullptr, size_t topn_work_bytes = 0, double outside_mul = 0.0);
 
-// ---- the fused roundtrip: one call, checked (rt_check), then run by one of four strategies (roundtrip_core) ----
+// ---- the fused roundtrip: one call record (RtCall), filled by its entry, checked (rt_check), then run by one strategy (roundtrip_core) ----
 // DSPFFT_NO_FUSED_ROUNDTRIP=1: no fused column kernel and no slices.  Read on every call (tests toggle it inside one process).
 bool fused_roundtrip_off() { const char *e = getenv("DSPFFT_NO_FUSED_ROUNDTRIP"); return e && *e == '1'; }
 
-void motion_filter_of(const dspfft_motion_filter_params &fp, MotionFilter &mf) { motion_filter_from(fp, mf); }
+// a call's filter parameters, checked, as the kernels take them (fp NULL: no filter, mf all zero); what: the caller's name in the message, or NULL
+int motion_filter_of(const dspfft_motion_filter_params *fp, MotionFilter &mf, const char *what = nullptr)
+{
+	memset((void *)&mf, 0, sizeof mf);
+	if (!fp) return 0;
+	if (fp->preserve_dc < 0 || fp->preserve_dc > 2 || fp->minbuf_hw[0] < 1 || fp->minbuf_hw[1] < 1 || fp->block_depth < 1) return fail(-1, "%s%sbad filter parameters", what ? what : "", what ? ": " : "");
+	motion_filter_from(*fp, mf);
+	return 0;
+}
+bool extents_differ(const dspfft_plan_s *fwd, const dspfft_plan_s *inv) { return fwd->rank != inv->rank || !std::equal(fwd->n, fwd->n + fwd->rank, inv->n); }
 
 // The blocks of a plan pair as motion.c:652-668 sees them: `nblocks` runs of `count` floats (a block's whole embedding, :657), `stride` apart
 // in the working buffer.  False when the blocks are no such runs (interleaved batches, blocks lying side by side in a volume).
@@ -1801,15 +1807,20 @@ bool topn_runs_of(const dspfft_plan_s *fwd, const dspfft_plan_s *inv, TopnRuns &
 	return true;
 }
 
-// One roundtrip call: its arguments, and what rt_check derives from them for the runners.
+// One roundtrip call as its entry fills it: zero but for what the entry has.
 // d_in8 / d_out8 non-NULL: 8-bit samples at the two ends (dspfft_execute_roundtrip_u8), d_out is then the float work buffer.
-struct RtCall {
+struct RtArgs {
 	dspfft_plan fwd, inv;
-	const float *d_in; float *d_out; const uint8_t *d_in8; uint8_t *d_out8; double mul8;
+	const float *d_in; float *d_out; const uint8_t *d_in8; uint8_t *d_out8; double mul8 = 1.0;
 	const dspfft_motion_filter_params *fp; unsigned long long *coded; void *stream;
-	size_t keep; void *topn_work; size_t topn_work_bytes;       // motion --coeff-limit (dspfft_execute_roundtrip_topn); keep = 0: none
+	size_t keep; void *topn_work; size_t topn_work_bytes;       // motion --coeff-limit (rt_limit); keep = 0: none
 	double outside_mul;                   // > 0: the call came through a dspfft_execute_roundtrip*_limit entry, which takes a limit on a rescaled block grid
-	// what rt_check adds (zero before)
+	Dither dither;                        // out8 non-NULL (d_out8 NULL): the inverse ends in d_out as floats and the dither kernel stores the bytes from there
+	const dspfft_motion_packed *packed;   // non-NULL: dspfft_execute_roundtrip_u8_packed's call, d_in8 / d_out8 hold packed->components bytes per pixel
+	bool may_slice = true;                // false: a slice of a clip (roundtrip_sliced)
+};
+// ... and what rt_check derives from them for the runners (zero before)
+struct RtCall : RtArgs {
 	const Pass *F, *I;                    // the forward plan's last pass and the inverse plan's first
 	bool rescale;                         // the inverse runs over other extents than the forward
 	bool block;                           // small blocks on aligned buffers: the fused block pass runs the call
@@ -1820,15 +1831,22 @@ struct RtCall {
 	MotionFilter mf;
 	TopnRuns runs;                        // keep != 0 and not `block`: the blocks as contiguous runs of the working buffer
 	U8Trc trc_in, trc_out;                // dspfft_plan_set_u8_trc of the forward plan (8-bit input) and of the inverse plan (8-bit or dithered output)
-	bool dithered;                        // set by roundtrip_core before rt_check: the bytes come from the dither kernel
 	bool grid;                            // a rescaled block grid (rt_grid): block_rescale.hip's kernel runs the call, out of place
-	BlockRsArgs rs;                       // its arguments, with the geometry derived for the pair
-	int rs_nwg; size_t rs_lds;
-	size_t rs_keep;                       // ... and its coefficient limit (0: none; block_rescale_topn.hip's kernel otherwise)
+	BlockRsTopnArgs rs;                   // its arguments, with the geometry derived for the pair (keep = 0: no coefficient limit; block_rescale_topn.hip's kernel otherwise)
 	bool temporal;                        // blocks along time that the plans' own passes cannot run (rt_temporal): temporal_rt.hip's kernel runs the call
 	TemporalArgs tp;                      // its arguments but the tables (rt_run_temporal)
-	int tp_nwg;
+	BlockPackedArgs pk;                   // packed pixels (rt_packed): block_packed.hip's kernel runs the call
+	int nwg; size_t lds;                  // the launch of the grid's, the temporal blocks' or the packed pixels' one kernel
 };
+// the dspfft_coeff_limit of a dspfft_execute_roundtrip*_limit entry into its call: what every such entry refuses of it comes first
+int rt_limit(RtCall &c, const dspfft_coeff_limit *cl)
+{
+	if (!cl) return fail(-1, "coefficient limit: null dspfft_coeff_limit (the entries without one take none)");
+	if (!cl->keep) return fail(-1, "coefficient limit: keep must be at least 1 (the entries without a dspfft_coeff_limit take none)");
+	if (!std::isfinite(cl->outside_mul) || !(cl->outside_mul > 0)) return fail(-1, "coefficient limit: outside_mul must be finite and > 0 (1 for motion's 3-D blocks)");
+	c.keep = cl->keep; c.topn_work = cl->d_work; c.topn_work_bytes = cl->work_bytes; c.outside_mul = cl->outside_mul;
+	return 0;
+}
 // the conversions at the ends of the unfused paths, plain or through the call's transfer characteristic
 int rt_u8_in(const RtCall &c, float *dst, uint64_t len)
 {
@@ -1839,27 +1857,29 @@ int rt_u8_out(const RtCall &c, const float *src, uint64_t len)
 	return c.trc_out.id ? dspfft_u8_trc_flat_launch(c.d_out8, src, c.mul8, len, 1, c.trc_out.id, c.trc_out.tab, c.stream) : be_f32_to_u8(c.d_out8, src, c.mul8, len, c.stream);
 }
 
-// ---- what rt_check and rt_grid both ask of a call ----
-// the filter's parameters, checked, as the kernels take them (c.mf all zero: no filter)
-int rt_filter(RtCall &c)
-{
-	memset(&c.mf, 0, sizeof c.mf);
-	if (!c.fp) return 0;
-	if (c.fp->preserve_dc < 0 || c.fp->preserve_dc > 2 || c.fp->minbuf_hw[0] < 1 || c.fp->minbuf_hw[1] < 1 || c.fp->block_depth < 1) return fail(-1, "bad filter parameters");
-	motion_filter_of(*c.fp, c.mf);
-	return 0;
-}
+// ---- what the checkers of the strategies share ----
+int rt_filter(RtCall &c, const char *what = nullptr) { return motion_filter_of(c.fp, c.mf, what); }
 // motion --linear: a plan's transfer characteristic acts where the call has an 8-bit end for it
 void rt_trc_ends(RtCall &c)
 {
 	if (c.d_in8 && c.fwd->u8_trc) c.trc_in = U8Trc{c.fwd->u8_trc, c.fwd->u8_tab};
-	if ((c.d_out8 || c.dithered) && c.inv->u8_trc) c.trc_out = U8Trc{c.inv->u8_trc, c.inv->u8_tab};
+	if ((c.d_out8 || c.dither.out8) && c.inv->u8_trc) c.trc_out = U8Trc{c.inv->u8_trc, c.inv->u8_tab};
 }
+// ... and its tables, for a fused kernel's arguments (the store has a table only where the kernel stores bytes itself: not ahead of the dither kernel)
+template <class Args> void rt_tables(const RtCall &c, Args &a) { a.tab_in = (const TrcU8Tab *)c.trc_in.tab; a.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; a.trc_out = c.trc_out.id; }
+// the call's buffers for a fused kernel's arguments: floats or bytes at either end
+template <class Args> void rt_buffers(const RtCall &c, Args &a) { a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8; }
 // the fused block kernels move float4s and packed words of four bytes at the two ends
 bool rt_ends_aligned(const RtCall &c)
 {
 	const uintptr_t pin = c.d_in8 ? (uintptr_t)c.d_in8 : (uintptr_t)c.d_in, pout = c.d_out8 ? (uintptr_t)c.d_out8 : (uintptr_t)c.d_out;
 	return !((c.d_in8 ? 3u : 15u) & pin) && !((c.d_out8 ? 3u : 15u) & pout);
+}
+// the largest group of at most G blocks whose tile leaves room for the tables and the counter in a workgroup's 64 KB of LDS; 0: not even one block does
+int rt_lds_group(int G, size_t block_bytes)
+{
+	while (G > 0 && (size_t)G * block_bytes + sizeof(TrcU8Tab) + 16 > 64 * 1024) G--;
+	return G;
 }
 // The arguments every fused block roundtrip shares: the forward plan's geometry with the inverse plan's output strides spliced in, the
 // call's buffers, the two plans' scales, the filter (rt_filter has run) and the counter.
@@ -1869,7 +1889,7 @@ void rt_block_args(const RtCall &c, BlockRtArgs &a)
 	const BlockGeom &o = c.inv->blk;
 	a.sy_out = o.sy_out; a.sz_out = o.sz_out; a.sxb_out = o.sxb_out;
 	for (int d = 0; d < o.nd; d++) a.bos[d] = o.bos[d];
-	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
+	rt_buffers(c, a);
 	block_scales(c.fwd, a.f); block_scales(c.inv, a.i);
 	a.filt = c.mf; a.coded = c.coded;
 }
@@ -1881,9 +1901,7 @@ void rt_block_args(const RtCall &c, BlockRtArgs &a)
 int rt_grid(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
-	bool differs = fwd->rank != inv->rank;
-	for (int a = 0; !differs && a < fwd->rank; a++) differs = fwd->n[a] != inv->n[a];
-	if (!differs || fwd->howmany < 2 || inv->howmany < 2) return 0;
+	if (!extents_differ(fwd, inv) || fwd->howmany < 2 || inv->howmany < 2) return 0;
 	const char *const what = "roundtrip with different forward / inverse extents over a grid of blocks";
 	if (fwd->rank != inv->rank) return fail(-2, "%s: the plans have different ranks (%d-D blocks against %d-D blocks)", what, fwd->rank, inv->rank);
 	if (!fwd->has_block || !inv->has_block)
@@ -1897,22 +1915,26 @@ int rt_grid(RtCall &c)
 	if (!same || fwd->howmany != inv->howmany) return fail(-2, "%s: the plans count different numbers of blocks", what);
 	if (!dspfft_block_rescale_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale.hip)", what);
 	const int mx = std::max(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
+	unsigned int limit = 0;
 	if (c.keep && c.keep < (size_t)mx * my * mz) {
 		// (the entries without dspfft_coeff_limit have no outside_mul to rank the coefficients outside min(block, scaled) with)
 		if (!(c.outside_mul > 0))
 			return fail(-2, "%s: a coefficient limit is not implemented here (the reference selects over the whole embedding, motion.c:652-668)", what);
 		if (!dspfft_block_rescale_topn_launch) return fail(-3, "%s with a coefficient limit: not built into this library (the kernel is HIP-only, block_rescale_topn.hip)", what);
-		c.rs_keep = c.keep;
+		limit = (unsigned int)c.keep;
 	}
 	c.keep = 0;
 	if (!rt_ends_aligned(c)) return fail(-2, "%s: float buffers must be 16-byte aligned, 8-bit buffers 4-byte aligned", what);
 	if (int rc = rt_filter(c)) return rc;
 	rt_trc_ends(c);
-	BlockRsArgs &r = c.rs;
-	memset(&r, 0, sizeof r);
+	BlockRsTopnArgs &r = c.rs;
+	memset((void *)&r, 0, sizeof r);
 	rt_block_args(c, r);
 	r.ox = i.nx; r.oy = i.ny; r.oz = i.nz;
-	r.tab_in = (const TrcU8Tab *)c.trc_in.tab; r.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; r.trc_out = c.trc_out.id;
+	// what the reference ranks outside min(block, scaled): the coefficient without the forward plan's scales, times outside_mul (block_rs_core.h)
+	r.keep = limit; r.key_mul = limit ? (float)(c.outside_mul / (double)r.f.scale) : 0.f;
+	for (int k = 0; k < 3; k++) r.key_mul0[k] = 1.f / r.f.out0[k];
+	rt_tables(c, r);
 	// blocks per workgroup: build_block's rule on the embedding with tiles of twice the size -- about 8192 samples (32 KB), rows of at most
 	// 1 KB.  The pruned phases have min(block, scaled) columns per block, so build_block's 4096 samples leave half the workgroup idle in them
 	// (1920x1080x64, 8-bit: 8x8x8 -> 4x4x4 1.17 -> 1.43 TB/s, 16x16x16 -> 8x8x8 0.92 -> 1.29, profiles/r09_motion_block_rescale.txt).  The
@@ -1923,13 +1945,12 @@ int rt_grid(RtCall &c)
 		G = env_int("DSPFFT_BLOCK_G");
 	}
 	if (G < 1) G = std::min(256 / mx, 8192 / (mx * my * mz));
-	G = std::max(1, std::min(G, f.nxb));
-	while (G > 1 && (size_t)mz * my * G * mx * sizeof(float) + sizeof(TrcU8Tab) + 16 > 64 * 1024) G--;
+	G = std::max(1, rt_lds_group(std::max(1, std::min(G, f.nxb)), (size_t)mz * my * mx * sizeof(float)));
 	r.tw = mx; r.G = G; r.pitch = G * mx; r.ngroups = (f.nxb + G - 1) / G; r.gdiv = make_div((uint32_t)r.ngroups);
 	long long nwg = r.ngroups;
 	for (int d = 0; d < r.nd; d++) nwg *= r.bn[d];
 	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch", what);
-	c.rs_nwg = (int)nwg; c.rs_lds = (size_t)mz * my * r.pitch * sizeof(float);
+	c.nwg = (int)nwg; c.lds = (size_t)mz * my * r.pitch * sizeof(float);
 	c.grid = true;
 	return 1;
 }
@@ -1938,18 +1959,11 @@ int rt_grid(RtCall &c)
 // into the inverse plan's output layout
 int rt_run_grid(const RtCall &c)
 {
-	if (c.rs_keep) {
-		// what the reference ranks outside min(block, scaled): the coefficient without the forward plan's scales, times outside_mul (block_rs_core.h)
-		BlockRsTopnArgs t;
-		memset((void *)&t, 0, sizeof t);
-		static_cast<BlockRsArgs &>(t) = c.rs;
-		t.keep = (unsigned int)c.rs_keep;
-		t.key_mul = (float)(c.outside_mul / (double)c.rs.f.scale);
-		for (int k = 0; k < 3; k++) t.key_mul0[k] = 1.f / c.rs.f.out0[k];
-		if (int rc = dspfft_block_rescale_topn_launch(&t, c.rs_nwg, c.rs_lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid with a coefficient limit): backend code %d", rc);
+	if (c.rs.keep) {
+		if (int rc = dspfft_block_rescale_topn_launch(&c.rs, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid with a coefficient limit): backend code %d", rc);
 		return 0;
 	}
-	if (int rc = dspfft_block_rescale_launch(&c.rs, c.rs_nwg, c.rs_lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid): backend code %d", rc);
+	if (int rc = dspfft_block_rescale_launch(&c.rs, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (rescaled block grid): backend code %d", rc);
 	return 0;
 }
 
@@ -2005,7 +2019,7 @@ int rt_temporal(RtCall &c)
 	if (!rt_temporal_pair(c.fwd, c.inv, t)) return 0;
 	if (int rc = rt_filter(c)) return rc;
 	const bool u8 = c.d_in8 || c.d_out8, positional = c.fp && !c.mf.quant_only;
-	if (c.dithered || (!u8 && t.D == t.S && !positional)) return 0;      // (roundtrip_dither sends a temporal pair's call here as the plain 8-bit one)
+	if (c.dither.out8 || (!u8 && t.D == t.S && !positional)) return 0;      // (roundtrip_dither sends a temporal pair's call here as the plain 8-bit one)
 	const char *const what = "roundtrip over blocks along time (motion -b 1x1xD)";
 	const int m = std::max(t.D, t.S);
 	if (c.keep && c.keep < (size_t)m) return fail(-2, "%s: a coefficient limit is not implemented here", what);
@@ -2025,13 +2039,13 @@ int rt_temporal(RtCall &c)
 	memset((void *)&a, 0, sizeof a);
 	a.D = t.D; a.S = t.S; a.K = K; a.B = K / 2; a.P = t.P; a.ntiles = (int)ntiles;
 	a.blk_in = (long long)t.D * t.P; a.blk_out = (long long)t.S * t.P;
-	a.in = c.d_in8 ? nullptr : c.d_in; a.out = c.d_out8 ? nullptr : c.d_out; a.in8 = c.d_in8; a.out8 = c.d_out8; a.mul8 = c.mul8;
+	rt_buffers(c, a);
 	a.f_scale = (float)c.fwd->scale; a.f_in0 = (float)c.fwd->in0[0]; a.f_out0 = (float)c.fwd->out0[0];
 	a.i_scale = (float)c.inv->scale; a.i_in0 = (float)c.inv->in0[0]; a.i_out0 = (float)c.inv->out0[0];
 	a.filt = c.mf; a.coded = c.coded;
-	a.tab_in = (const TrcU8Tab *)c.trc_in.tab; a.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; a.trc_out = c.trc_out.id;
+	rt_tables(c, a);
 	a.divB = make_div((uint32_t)a.B); a.divQ = make_div((uint32_t)(K / 4)); a.div_tiles = make_div((uint32_t)a.ntiles);
-	c.tp_nwg = (int)nwg;
+	c.nwg = (int)nwg;
 	c.temporal = true;
 	return 1;
 }
@@ -2062,7 +2076,53 @@ int rt_run_temporal(const RtCall &c)
 	a.ff = F.pa.fft; a.fi = I.pa.fft;
 	a.Tf = (const cx<float> *)F.tab.T; a.Wf = (const cx<float> *)F.tab.W; a.posf = (const uint32_t *)F.tab.pos;
 	a.Ti = (const cx<float> *)I.tab.T; a.Wi = (const cx<float> *)I.tab.W; a.posi = (const uint32_t *)I.tab.pos;
-	if (int rc = dspfft_temporal_rt_launch(&a, c.tp_nwg, c.stream)) return fail(-4, "kernel launch failed (blocks along time): backend code %d", rc);
+	if (int rc = dspfft_temporal_rt_launch(&a, c.nwg, c.stream)) return fail(-4, "kernel launch failed (blocks along time): backend code %d", rc);
+	return 0;
+}
+
+// ---- motion on packed 8-bit pixels (rgb24, rgba ...; include/dspfft.h): the planar small-block pair's geometry with every stride and offset
+// times `components`, block_packed.hip's kernel.  The entry has refused null plans, buffers and c.packed, f64 plans and a limit of 0; the rest
+// of the call is checked here, the library's own lack of the kernel last.  0: c.pk is set; < 0: the call cannot run.  Nothing is launched here.
+constexpr const char *kPacked = "roundtrip on packed 8-bit pixels";
+int rt_packed(RtCall &c)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const char *const what = kPacked;
+	if (int rc = rt_filter(c, what)) return rc;
+	const int C = c.packed->components;
+	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
+	if (extents_differ(fwd, inv) && fwd->has_block && inv->has_block) return fail(-2, "%s: different forward / inverse extents (a rescaled block grid, motion -s) are not implemented on packed pixels", what);
+	if (!block_roundtrip_ok(fwd, inv))
+		return fail(-2, "%s needs the plan pair of the fused block pass: matching REDFT10 / REDFT01 small-block plans (every extent 4, 8 or 16, 2-D blocks up to 32; per-frame and single-block plans have no block pass)", what);
+	if (!rt_ends_aligned(c)) return fail(-2, "%s: the buffers must be 4-byte aligned", what);
+	rt_trc_ends(c);
+	BlockPackedArgs &a = c.pk;
+	memset((void *)&a, 0, sizeof a);
+	rt_block_args(c, a);
+	rt_tables(c, a);
+	// the plans count pixels; the kernel addresses bytes
+	a.sy_in *= C; a.sz_in *= C; a.sxb_in *= C; a.sy_out *= C; a.sz_out *= C; a.sxb_out *= C;
+	long long nwg = 1;
+	for (int d = 0; d < a.nd; d++) { a.bis[d] *= C; a.bos[d] *= C; nwg *= a.bn[d]; }
+	int G = packed_group_of(a.nx, a.ny, a.nz, C, a.nxb);
+	if (const char *e = getenv("DSPFFT_PACKED_G")) { if (atoi(e) > 0) G = std::min(atoi(e), a.nxb); }      // experiments (tools/bench_motion_packed.py)
+	const size_t block_bytes = (size_t)a.nz * a.ny * C * a.nx * sizeof(float);
+	G = rt_lds_group(G, block_bytes);
+	if (!G) return fail(-2, "%s: the %d component tiles of a %dx%dx%d block (%zu bytes) and the tables do not fit a workgroup's 64 KB of LDS", what, C, a.nx, a.ny, a.nz, block_bytes);
+	a.G = G; a.pitch = G * C * a.nx; a.ngroups = (a.nxb + G - 1) / G; a.gdiv = make_div((uint32_t)a.ngroups);
+	nwg *= a.ngroups;
+	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch (more than 2^31 - 1 workgroups)", what);
+	a.comps = C;
+	if (c.fp) for (int k = 0; k < C; k++) { a.damp[k] = c.packed->damp[k]; a.boost[k] = c.packed->boost[k]; a.grey_add[k] = c.packed->grey_add[k]; }
+	// --coeff-limit: at or above the block's count nothing is dropped (motion.c:654-657) and the call is the plain one
+	a.keep = c.keep < (size_t)a.nx * a.ny * a.nz ? (unsigned int)c.keep : 0;
+	if (!dspfft_block_packed_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_packed.hip)", what);
+	c.nwg = (int)nwg; c.lds = (size_t)G * block_bytes;
+	return 0;
+}
+int rt_run_packed(const RtCall &c)
+{
+	if (int rc = dspfft_block_packed_launch(&c.pk, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (%s): backend code %d", kPacked, rc);
 	return 0;
 }
 
@@ -2071,6 +2131,7 @@ int rt_check(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
 	const dspfft_motion_filter_params *fp = c.fp;
+	if (c.packed) return rt_packed(c);                         // (its entry takes no other strategy, and has seen to plans and buffers)
 	if (!fwd || !inv || !(c.d_in || c.d_in8) || !(c.d_out || c.d_out8)) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
 	if (int t = rt_temporal(c)) return t < 0 ? t : 0;          // (ahead of rt_grid, which answers every rescaled pair with batches that it is no grid)
@@ -2078,10 +2139,8 @@ int rt_check(RtCall &c)
 	if (!c.d_out) return fail(-1, "null plan or buffer");       // (only a rescaled block grid and blocks along time store their bytes without a float work buffer)
 	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
 	const Pass &F = *(c.F = &fwd->passes[nf - 1]), &I = *(c.I = &inv->passes[0]);
-	bool differs = fwd->rank != inv->rank;
-	for (int a = 0; !differs && a < fwd->rank; a++) differs = fwd->n[a] != inv->n[a];
 	// (plans whose blocks go through the fused block pass have no pass order to agree on)
-	if (fwd->rank != inv->rank || fwd->howmany != inv->howmany || (!differs && F.axis != I.axis && !block_roundtrip_ok(fwd, inv)))
+	if (fwd->rank != inv->rank || fwd->howmany != inv->howmany || (!extents_differ(fwd, inv) && F.axis != I.axis && !block_roundtrip_ok(fwd, inv)))
 		return fail(-1, "the forward plan's last pass and the inverse plan's first pass must run along the same axis (create the inverse with dspfft_plan_many_r2r_ordered(..., 1))");
 	// motion's `scaled != block` (motion.c:535-552): the inverse runs over DIFFERENT extents inside the same embedding -- larger:
 	// the spectrum is zero-padded (band-limited upscale), smaller: truncated (downscale)
@@ -2156,24 +2215,15 @@ int rt_check(RtCall &c)
 // small blocks: everything in one pass over the data
 int rt_run_block(const RtCall &c)
 {
-	BlockRtArgs a;
-	rt_block_args(c, a);
+	BlockRtTrcArgs t;          // the arguments of the three kernels: each launcher takes the base it knows
+	rt_block_args(c, t);
+	t.keep = (unsigned int)c.keep;
+	rt_tables(c, t);
 	if (c.trc_in.id || c.trc_out.id) {
-		BlockRtTrcArgs t;
-		static_cast<BlockRtArgs &>(t) = a;
-		t.keep = (unsigned int)c.keep;
-		t.tab_in = (const TrcU8Tab *)c.trc_in.tab; t.tab_out = c.d_out8 ? (const TrcU8Tab *)c.trc_out.tab : nullptr; t.trc_out = c.trc_out.id;
 		if (int rc = dspfft_block_trc_launch(&t, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip with a transfer characteristic): backend code %d", rc);
-		return 0;
-	}
-	if (c.keep) {
-		BlockRtTopnArgs t;
-		static_cast<BlockRtArgs &>(t) = a;
-		t.keep = (unsigned int)c.keep;
+	} else if (c.keep) {
 		if (int rc = dspfft_block_topn_launch(&t, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip with a coefficient limit): backend code %d", rc);
-		return 0;
-	}
-	if (int rc = be_launch_block_roundtrip(a, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip): backend code %d", rc);
+	} else if (int rc = be_launch_block_roundtrip(t, c.fwd->blk_nwg, c.fwd->blk_lds, c.stream)) return fail(-4, "kernel launch failed (fused block roundtrip): backend code %d", rc);
 	return 0;
 }
 
@@ -2245,11 +2295,7 @@ int rt_run_passes(const RtCall &c)
 	for (size_t i = 0; i + 1 < nf; i++) {
 		const Pass &P = fwd->passes[i];
 		if (i == 0 && c.d_in8 && c.u8_first) {
-			U8IO io; io.in = c.d_in8; io.out = nullptr; io.mul = 1.0;
-			if (c.trc_in.id) {
-				U8IOTrc t; static_cast<U8IO &>(t) = io; t.tab_in = (const TrcU8Tab *)c.trc_in.tab;
-				if (int rc = run_pass_u8_trc(fwd, P, d_out, d_out, false, t, stream)) return rc;
-			} else if (int rc = run_pass_u8(fwd, P, d_out, d_out, false, io, stream)) return rc;
+			if (int rc = run_pass_u8(fwd, P, d_out, U8IO{c.d_in8, nullptr, 1.0}, c.trc_in, stream)) return rc;
 			continue;
 		}
 		if (int rc = run_pass<float>(fwd, P, P.first ? d_in : d_out, d_out, false, stream)) return rc;
@@ -2272,11 +2318,7 @@ int rt_run_passes(const RtCall &c)
 	for (size_t i = 1; i < ni; i++) {
 		const Pass &P = inv->passes[i];
 		if (i + 1 == ni && c.d_out8 && c.u8_last) {
-			U8IO io; io.in = nullptr; io.out = c.d_out8; io.mul = c.mul8;
-			if (c.trc_out.id) {
-				U8IOTrc t; static_cast<U8IO &>(t) = io; t.tab_out = (const TrcU8Tab *)c.trc_out.tab; t.trc_out = c.trc_out.id;
-				if (int rc = run_pass_u8_trc(inv, P, d_out, d_out, true, t, stream)) return rc;
-			} else if (int rc = run_pass_u8(inv, P, d_out, d_out, true, io, stream)) return rc;
+			if (int rc = run_pass_u8(inv, P, d_out, U8IO{nullptr, c.d_out8, c.mul8}, c.trc_out, stream)) return rc;
 			continue;
 		}
 		if (int rc = run_pass<float>(inv, P, (const float *)d_out, d_out, i + 1 == ni, stream)) return rc;
@@ -2347,15 +2389,15 @@ dspfft_plan_s *slice_plan(const dspfft_plan_s *of, int frames)
 	dspfft_plan out = nullptr;
 	return plan_finish(pl, &out, of->first_axis_first) ? nullptr : out;
 }
-// the parent's scales may have been set since its slice plans were made (dspfft_plan_set_scale / _set_axis_scale0)
-void follow_scales(std::initializer_list<dspfft_plan_s *> slices, const dspfft_plan_s *of)
+// the parent's scales may have been set since its slice plans were made (dspfft_plan_set_scale / _set_axis_scale0), and its transfer
+// characteristic (dspfft_plan_set_u8_trc); the tables stay the parent's
+void follow_parent(std::initializer_list<dspfft_plan_s *> slices, const dspfft_plan_s *of)
 {
-	for (dspfft_plan_s *q : slices) if (q) { q->scale = of->scale; for (int a = 0; a < 2; a++) { q->in0[a] = of->in0[a]; q->out0[a] = of->out0[a]; } }
-}
-// ... and its transfer characteristic (dspfft_plan_set_u8_trc); the tables stay the parent's
-void follow_trc(std::initializer_list<dspfft_plan_s *> slices, const dspfft_plan_s *of)
-{
-	for (dspfft_plan_s *q : slices) if (q) { q->u8_trc = of->u8_trc; q->u8_tab = of->u8_tab; }
+	for (dspfft_plan_s *q : slices) {
+		if (!q) continue;
+		q->scale = of->scale; q->u8_trc = of->u8_trc; q->u8_tab = of->u8_tab;
+		for (int a = 0; a < 2; a++) { q->in0[a] = of->in0[a]; q->out0[a] = of->out0[a]; }
+	}
 }
 // From the fork on, the join of the library's stream: on every way out of roundtrip_sliced the caller's stream waits for what the side stream
 // was given, so that nothing of this call writes the caller's buffers once the caller's stream is through.  (Sets no error text: the first
@@ -2374,7 +2416,8 @@ struct SideJoin {
 };
 
 // returns 1 when the clip was run in slices, 0 when this call does not qualify (the caller runs it whole), < 0 on error
-int roundtrip_sliced(const RtCall &c, const Dither *dither)
+int roundtrip_core(RtCall &c);
+int roundtrip_sliced(const RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
 	const int S = slice_frames(fwd, inv, c.fp);
@@ -2398,10 +2441,8 @@ int roundtrip_sliced(const RtCall &c, const Dither *dither)
 		r = n.get();
 		fwd->rt_slices.push_back(std::move(n));
 	}
-	follow_scales({r->fwd, r->fwd_rem}, fwd);
-	follow_scales({r->inv, r->inv_rem}, inv);
-	follow_trc({r->fwd, r->fwd_rem}, fwd);
-	follow_trc({r->inv, r->inv_rem}, inv);
+	follow_parent({r->fwd, r->fwd_rem}, fwd);
+	follow_parent({r->inv, r->inv_rem}, inv);
 	const long long fin = fwd->batches[0].is, fwk = fwd->batches[0].os, fout = inv->batches[0].os;
 	const bool two = r->side != nullptr;
 	if (two && (be_event_record(r->ev_fork, c.stream) || be_stream_wait_event(r->side, r->ev_fork))) return fail(-4, "stream fork failed");
@@ -2409,36 +2450,62 @@ int roundtrip_sliced(const RtCall &c, const Dither *dither)
 	int k = 0;
 	for (int f0 = 0; f0 < total; f0 += S, k++) {
 		const bool last = total - f0 < S, odd = two && (k & 1);
-		// dithered: each slice's planes (whole frames) are dithered on the slice's stream before its work area is reused
-		Dither ds;
-		if (dither) { ds = *dither; ds.out8 += (long long)f0 * fout; }
-		if (int rc = roundtrip_core(last ? r->fwd_rem : r->fwd, last ? r->inv_rem : r->inv, nullptr, c.d_out + (odd ? (long long)S * fwk : 0), c.d_in8 + (long long)f0 * fin,
-		                            c.d_out8 ? c.d_out8 + (long long)f0 * fout : nullptr, c.mul8, c.fp, c.coded, odd ? r->side : c.stream, false, dither ? &ds : nullptr)) return rc;
+		// the clip's call on the slice's plans, frames, work area and stream: each slice's planes (whole frames) are stored or dithered on the
+		// slice's stream before its work area is reused
+		RtCall s = {};
+		static_cast<RtArgs &>(s) = c;
+		s.fwd = last ? r->fwd_rem : r->fwd; s.inv = last ? r->inv_rem : r->inv; s.stream = odd ? r->side : c.stream; s.may_slice = false;
+		s.d_out = c.d_out + (odd ? (long long)S * fwk : 0); s.d_in8 = c.d_in8 + (long long)f0 * fin;
+		if (c.d_out8) s.d_out8 = c.d_out8 + (long long)f0 * fout;
+		if (c.dither.out8) s.dither.out8 = c.dither.out8 + (long long)f0 * fout;
+		if (int rc = roundtrip_core(s)) return rc;
 	}
 	return side.join() ? fail(-4, "stream join failed") : 1;
 }
 
-// dither non-NULL (d_out8 NULL): the inverse transform ends in d_out as floats and the dither kernel stores dither->out8 from there.
-int roundtrip_core(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const uint8_t *d_in8, uint8_t *d_out8, double mul8,
-                   const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream, bool may_slice, const Dither *dither,
-                   size_t keep, void *topn_work, size_t topn_work_bytes, double outside_mul)
+// a call as its entry filled it: checked, then run by the one strategy that takes it
+int roundtrip_core(RtCall &c)
 {
-	RtCall c = {fwd, inv, d_in, d_out, d_in8, d_out8, mul8, fp, d_coeffs_coded, stream, keep, topn_work, topn_work_bytes, outside_mul};
-	c.dithered = dither != nullptr;
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
-	if (c.grid) rc = rt_run_grid(c);
+	if (c.packed) rc = rt_run_packed(c);
+	else if (c.grid) rc = rt_run_grid(c);
 	else if (c.temporal) rc = rt_run_temporal(c);
 	else if (c.block) rc = rt_run_block(c);
 	else if (c.rescale) rc = rt_run_rescale(c);
 	else {
-		if (may_slice && !c.keep && d_in8 && (d_out8 || dither) && c.u8_first && c.u8_last && c.F->axis == c.I->axis && (15u & (uintptr_t)d_out) == 0 && !fused_roundtrip_off())
-			rc = roundtrip_sliced(c, dither);
+		if (c.may_slice && !c.keep && c.d_in8 && (c.d_out8 || c.dither.out8) && c.u8_first && c.u8_last && c.F->axis == c.I->axis && (15u & (uintptr_t)c.d_out) == 0 &&
+		    !fused_roundtrip_off())
+			rc = roundtrip_sliced(c);
 		if (rc) return rc < 0 ? rc : 0;          // in slices: every slice has stored or dithered its own frames
 		rc = rt_run_passes(c);
 	}
-	if (rc || !dither) return rc;
-	return dither_store(inv, d_out, *dither, c.trc_out, stream);
+	if (rc || !c.dither.out8) return rc;
+	return dither_store(c.inv, c.d_out, c.dither, c.trc_out, c.stream);
+}
+
+// dspfft_execute_roundtrip_u8_dither and its twin with a coefficient limit: the call with the bytes' buffer and the two factors in c.dither
+int roundtrip_dither(RtCall &c)
+{
+	const Dither dz = c.dither;
+	if (!c.fwd || !c.inv || !c.d_in8 || !dz.out8) return fail(-1, "null plan or buffer");
+	// blocks along time: a 1 x 1 plane has no neighbour to diffuse into (the conditions of motion.c:781-785 are all false), so the bytes
+	// are the plain 8-bit call's with out_mul = scalefactor normalization^2 -- and that call needs no work buffer
+	TemporalPair tp;
+	const bool temporal = rt_temporal_pair(c.fwd, c.inv, tp);
+	if (!temporal) {
+		if (!c.d_out) return fail(-1, "null plan or buffer");
+		if (c.fwd->f64 || c.inv->f64) return fail(-1, "the dithered roundtrip takes f32 plans");
+		if (!dspfft_dither_launch) return fail(-3, "dithered 8-bit store: not in this build (the dither kernel is HIP-only, motion_dither.hip)");
+	}
+	if (!(dz.sf > 0) || !(dz.norm > 0)) return fail(-1, "dither: scalefactor and normalization must be > 0");
+	if (temporal) {
+		c.d_out8 = dz.out8; c.mul8 = dz.sf * dz.norm * dz.norm; c.dither = Dither{};
+		return roundtrip_core(c);
+	}
+	dspfft_dither_geom g;
+	if (int rc = dither_geom_of(c.inv, g)) return rc;
+	return roundtrip_core(c);
 }
 }  // namespace
 
@@ -2446,14 +2513,18 @@ extern "C" int dspfft_execute_roundtrip(dspfft_plan fwd, dspfft_plan inv, const 
                                         const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream)
 {
 	if (!d_in) return fail(-1, "null plan or buffer");
-	return roundtrip_core(fwd, inv, d_in, d_out, nullptr, nullptr, 1.0, fp, d_coeffs_coded, stream);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in = d_in; c.d_out = d_out; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
 }
 
 extern "C" int dspfft_execute_roundtrip_u8(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
                                            const dspfft_motion_filter_params *fp, unsigned long long *d_coeffs_coded, void *stream)
 {
 	if (!d_in || !d_out) return fail(-1, "null plan or buffer");         // (d_work: rt_check; a rescaled block grid needs none)
-	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.d_out = d_work; c.mul8 = out_mul; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
 }
 
 // ---- motion --spectrogram / --ispectrogram: the halves of the roundtrip, one plan each (include/dspfft.h) ----
@@ -2505,16 +2576,12 @@ int spec_passes(const SpecCall &c)
 		if (plane % hw[1] || plane / hw[1] < n3[1] || plane / hw[1] > 0x7fffffffLL) return fail(-2, "%s: %s", what, layout);
 		hw[0] = (int)(plane / hw[1]);
 	}
-	long long span = 1, dense = 1;
-	for (int a = 0; a < r; a++) { span += (long long)(pl->n[a] - 1) * pl->axes[a].os; dense *= pl->n[a]; }
-	std::vector<Dim> dims;
-	for (const Dim &b : pl->batches) if (b.n > 1) { if (b.is != b.os) return fail(-2, "%s: %s", what, layout); dims.push_back(b); }
-	merge_dims(dims);
-	if (dims.size() > 1 || (dims.size() == 1 && dims[0].os < span)) return fail(-2, "%s: %s", what, layout);
-	const size_t nblocks = dims.empty() ? 1 : (size_t)dims[0].n;
-	const long long stride = dims.empty() ? span : dims[0].os;
-	dense *= (long long)nblocks;
-	span += (long long)(nblocks - 1) * stride;
+	for (const Dim &b : pl->batches) if (b.n > 1 && b.is != b.os) return fail(-2, "%s: %s", what, layout);
+	TopnRuns runs;          // the blocks of the batch: one run each
+	if (!topn_runs_of(pl, pl, runs)) return fail(-2, "%s: %s", what, layout);
+	const long long span = (long long)runs.count + (long long)(runs.nblocks - 1) * runs.stride;
+	long long dense = (long long)runs.nblocks;
+	for (int a = 0; a < r; a++) dense *= pl->n[a];
 	const size_t np = pl->passes.size();
 	// the 8-bit end on the transform's side: the first (last) pass where it is a planar row pass with an 8-bit kernel, else one sweep
 	const bool fused8 = c.u8 && np >= 2 && pass_has_u8(pl, pl->passes[c.inverse ? np - 1 : 0]);
@@ -2522,7 +2589,7 @@ int spec_passes(const SpecCall &c)
 	float *const w = c.d_work;
 	const dspfft_motion_spec_params plain_in = {DSPFFT_MOTION_NONE, 1.0, 1.0, 0.0}, plain_out = {DSPFFT_MOTION_NONE, c.out_mul, 1.0, 0.0};
 	auto blocks = [&](int inverse, void *pix, const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *fp, unsigned long long *coded) {
-		if (dspfft_spec_blocks_launch(inverse, c.u8, pix, w, n3, hw, nblocks, stride, sp, fp, coded, c.stream))
+		if (dspfft_spec_blocks_launch(inverse, c.u8, pix, w, n3, hw, runs.nblocks, runs.stride, sp, fp, coded, c.stream))
 			return fail(-4, "%s: %s", what, dspfft_motion_last_error ? dspfft_motion_last_error() : "launch failed");
 		return 0;
 	};
@@ -2532,8 +2599,7 @@ int spec_passes(const SpecCall &c)
 		for (size_t i = 0; i < np; i++) {
 			const Pass &P = pl->passes[i];
 			if (i == 0 && fused8) {
-				U8IO io; io.in = (const uint8_t *)c.d_in; io.out = nullptr; io.mul = 1.0;
-				if (int rc = run_pass_u8(pl, P, w, w, false, io, c.stream)) return rc;
+				if (int rc = run_pass_u8(pl, P, w, U8IO{(const uint8_t *)c.d_in, nullptr, 1.0}, U8Trc(), c.stream)) return rc;
 			} else if (int rc = run_pass<float>(pl, P, (const float *)w, w, i + 1 == np, c.stream)) return rc;
 		}
 		return blocks(0, c.d_out, c.sp, c.fp, c.coded);
@@ -2542,8 +2608,7 @@ int spec_passes(const SpecCall &c)
 	for (size_t i = 0; i < np; i++) {
 		const Pass &P = pl->passes[i];
 		if (i + 1 == np && fused8) {
-			U8IO io; io.in = nullptr; io.out = (uint8_t *)c.d_out; io.mul = c.out_mul;
-			if (int rc = run_pass_u8(pl, P, w, w, true, io, c.stream)) return rc;
+			if (int rc = run_pass_u8(pl, P, w, U8IO{nullptr, (uint8_t *)c.d_out, c.out_mul}, U8Trc(), c.stream)) return rc;
 		} else if (int rc = run_pass<float>(pl, P, (const float *)w, w, i + 1 == np, c.stream)) return rc;
 	}
 	if (c.u8) return !fused8 && be_f32_to_u8((uint8_t *)c.d_out, w, c.out_mul, (uint64_t)span, c.stream) ? fail(-4, "launch failed") : 0;
@@ -2565,11 +2630,7 @@ int spec_core(const SpecCall &c)
 	for (int a = 0; a < pl->rank; a++)
 		if (pl->kinds[a] != (c.inverse ? DSPFFT_REDFT01 : DSPFFT_REDFT10)) return fail(-1, "%s: the plan must be %s on every axis", what, c.inverse ? "REDFT01" : "REDFT10");
 	MotionFilter mf;
-	memset((void *)&mf, 0, sizeof mf);
-	if (c.fp) {
-		if (c.fp->preserve_dc < 0 || c.fp->preserve_dc > 2 || c.fp->minbuf_hw[0] < 1 || c.fp->minbuf_hw[1] < 1 || c.fp->block_depth < 1) return fail(-1, "bad filter parameters");
-		motion_filter_of(*c.fp, mf);
-	}
+	if (int rc = motion_filter_of(c.fp, mf)) return rc;
 	if (pl->has_block) return spec_block(c, mf);
 	return spec_passes(c);
 }
@@ -2645,8 +2706,7 @@ int spec_image_core(const SpecImageCall &c)
 	const bool fused8 = !blocky && &passes == &pl->passes && dwords && pass_has_u8(pl, passes[c.inverse ? 1 : 0], true);
 	if (!c.inverse) {
 		if (fused8) {
-			U8IO io; io.in = c.d_in; io.out = nullptr; io.mul = 1.0;
-			if (int rc = run_pass_u8(pl, passes[0], wk, wk, false, io, c.stream)) return rc;
+			if (int rc = run_pass_u8(pl, passes[0], wk, U8IO{c.d_in, nullptr, 1.0}, U8Trc(), c.stream)) return rc;
 			if (int rc = run_pass<float>(pl, passes[1], (const float *)wk, wk, true, c.stream)) return rc;
 		} else {
 			if (be_u8_to_f32(wk, c.d_in, len, c.stream)) return fail(-4, "launch failed");
@@ -2666,8 +2726,7 @@ int spec_image_core(const SpecImageCall &c)
 	if (dspfft_spec_image_decode_launch(&e, c.stream)) return fail(-4, "ispec_u8: launch failed");
 	if (fused8) {
 		if (int rc = run_pass<float>(pl, passes[0], (const float *)wk, wk, false, c.stream)) return rc;
-		U8IO io; io.in = nullptr; io.out = c.d_out; io.mul = 255.0;
-		return run_pass_u8(pl, passes[1], wk, wk, true, io, c.stream);
+		return run_pass_u8(pl, passes[1], wk, U8IO{nullptr, c.d_out, 255.0}, U8Trc(), c.stream);
 	}
 	if (int rc = execute_t<float>(pl, wk, wk, c.stream)) return rc;
 	return be_f32_to_u8(c.d_out, wk, 255.0, len, c.stream) ? fail(-4, "launch failed") : 0;
@@ -2696,7 +2755,10 @@ extern "C" int dspfft_execute_roundtrip_topn(dspfft_plan fwd, dspfft_plan inv, c
                                              void *d_topn_work, size_t work_bytes, unsigned long long *d_coeffs_coded, void *stream)
 {
 	if (!d_in) return fail(-1, "null plan or buffer");
-	return roundtrip_core(fwd, inv, d_in, d_out, nullptr, nullptr, 1.0, fp, d_coeffs_coded, stream, true, nullptr, keep, d_topn_work, work_bytes);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in = d_in; c.d_out = d_out; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	c.keep = keep; c.topn_work = d_topn_work; c.topn_work_bytes = work_bytes;
+	return roundtrip_core(c);
 }
 
 extern "C" int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
@@ -2704,128 +2766,64 @@ extern "C" int dspfft_execute_roundtrip_u8_topn(dspfft_plan fwd, dspfft_plan inv
                                                 unsigned long long *d_coeffs_coded, void *stream)
 {
 	if (!d_in || !d_out) return fail(-1, "null plan or buffer");
-	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream, true, nullptr, keep, d_topn_work, work_bytes);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.d_out = d_work; c.mul8 = out_mul; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	c.keep = keep; c.topn_work = d_topn_work; c.topn_work_bytes = work_bytes;
+	return roundtrip_core(c);
 }
-
-namespace {
-// dspfft_execute_roundtrip_u8_dither and its twin with a coefficient limit (cl NULL: none)
-int roundtrip_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double scalefactor, double normalization,
-                     const dspfft_motion_filter_params *fp, const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
-{
-	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "null plan or buffer");
-	// blocks along time: a 1 x 1 plane has no neighbour to diffuse into (the conditions of motion.c:781-785 are all false), so the bytes
-	// are the plain 8-bit call's with out_mul = scalefactor normalization^2 -- and that call needs no work buffer
-	TemporalPair tp;
-	if (rt_temporal_pair(fwd, inv, tp)) {
-		if (!(scalefactor > 0) || !(normalization > 0)) return fail(-1, "dither: scalefactor and normalization must be > 0");
-		return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, scalefactor * normalization * normalization, fp, d_coeffs_coded, stream, true, nullptr,
-		                      cl ? cl->keep : 0, cl ? cl->d_work : nullptr, cl ? cl->work_bytes : 0, cl ? cl->outside_mul : 0.0);
-	}
-	if (!d_work) return fail(-1, "null plan or buffer");
-	if (fwd->f64 || inv->f64) return fail(-1, "the dithered roundtrip takes f32 plans");
-	if (!dspfft_dither_launch) return fail(-3, "dithered 8-bit store: not in this build (the dither kernel is HIP-only, motion_dither.hip)");
-	if (!(scalefactor > 0) || !(normalization > 0)) return fail(-1, "dither: scalefactor and normalization must be > 0");
-	dspfft_dither_geom g;
-	if (int rc = dither_geom_of(inv, g)) return rc;
-	const Dither dz = {d_out, scalefactor, normalization};
-	if (!cl) return roundtrip_core(fwd, inv, nullptr, d_work, d_in, nullptr, 1.0, fp, d_coeffs_coded, stream, true, &dz);
-	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, nullptr, 1.0, fp, d_coeffs_coded, stream, true, &dz, cl->keep, cl->d_work, cl->work_bytes, cl->outside_mul);
-}
-// what every dspfft_execute_roundtrip*_limit entry refuses of its dspfft_coeff_limit
-int coeff_limit_check(const dspfft_coeff_limit *cl)
-{
-	if (!cl) return fail(-1, "coefficient limit: null dspfft_coeff_limit (the entries without one take none)");
-	if (!cl->keep) return fail(-1, "coefficient limit: keep must be at least 1 (the entries without a dspfft_coeff_limit take none)");
-	if (!std::isfinite(cl->outside_mul) || !(cl->outside_mul > 0)) return fail(-1, "coefficient limit: outside_mul must be finite and > 0 (1 for motion's 3-D blocks)");
-	return 0;
-}
-}  // namespace
 
 extern "C" int dspfft_execute_roundtrip_u8_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
                                                   double scalefactor, double normalization, const dspfft_motion_filter_params *fp,
                                                   unsigned long long *d_coeffs_coded, void *stream)
 {
-	return roundtrip_dither(fwd, inv, d_in, d_out, d_work, scalefactor, normalization, fp, nullptr, d_coeffs_coded, stream);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out = d_work; c.dither = Dither{d_out, scalefactor, normalization}; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_dither(c);
 }
 
 extern "C" int dspfft_execute_roundtrip_limit(dspfft_plan fwd, dspfft_plan inv, const float *d_in, float *d_out, const dspfft_motion_filter_params *fp,
                                               const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
 {
-	if (int rc = coeff_limit_check(cl)) return rc;
+	RtCall c = {};
+	if (int rc = rt_limit(c, cl)) return rc;
 	if (!d_in) return fail(-1, "null plan or buffer");
-	return roundtrip_core(fwd, inv, d_in, d_out, nullptr, nullptr, 1.0, fp, d_coeffs_coded, stream, true, nullptr, cl->keep, cl->d_work, cl->work_bytes, cl->outside_mul);
+	c.fwd = fwd; c.inv = inv; c.d_in = d_in; c.d_out = d_out; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
 }
 
 extern "C" int dspfft_execute_roundtrip_u8_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
                                                  const dspfft_motion_filter_params *fp, const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
 {
-	if (int rc = coeff_limit_check(cl)) return rc;
+	RtCall c = {};
+	if (int rc = rt_limit(c, cl)) return rc;
 	if (!d_in || !d_out) return fail(-1, "null plan or buffer");
-	return roundtrip_core(fwd, inv, nullptr, d_work, d_in, d_out, out_mul, fp, d_coeffs_coded, stream, true, nullptr, cl->keep, cl->d_work, cl->work_bytes, cl->outside_mul);
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.d_out = d_work; c.mul8 = out_mul; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
 }
 
 extern "C" int dspfft_execute_roundtrip_u8_dither_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work,
                                                         double scalefactor, double normalization, const dspfft_motion_filter_params *fp,
                                                         const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
 {
-	if (int rc = coeff_limit_check(cl)) return rc;
-	return roundtrip_dither(fwd, inv, d_in, d_out, d_work, scalefactor, normalization, fp, cl, d_coeffs_coded, stream);
+	RtCall c = {};
+	if (int rc = rt_limit(c, cl)) return rc;
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out = d_work; c.dither = Dither{d_out, scalefactor, normalization}; c.fp = fp; c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_dither(c);
 }
 
-// motion on packed 8-bit pixels (rgb24, rgba ...; include/dspfft.h): the planar small-block pair's geometry with every stride and offset times
-// `components`, block_packed.hip's kernel.  Every check comes before the launch.
+// motion on packed 8-bit pixels (rt_packed).  cl NULL: no coefficient limit.
 extern "C" int dspfft_execute_roundtrip_u8_packed(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
                                                   const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed, const dspfft_coeff_limit *cl,
                                                   unsigned long long *d_coeffs_coded, void *stream)
 {
-	const char *const what = "roundtrip on packed 8-bit pixels";
-	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", what);
-	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", what);
-	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", what);
-	if (cl && !cl->keep) return fail(-1, "%s: coefficient limit: keep must be at least 1 (pass NULL for no limit)", what);
-	if (fp && (fp->preserve_dc < 0 || fp->preserve_dc > 2 || fp->minbuf_hw[0] < 1 || fp->minbuf_hw[1] < 1 || fp->block_depth < 1)) return fail(-1, "%s: bad filter parameters", what);
-	const int C = packed->components;
-	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
-	bool differs = fwd->rank != inv->rank;
-	for (int a = 0; !differs && a < fwd->rank; a++) differs = fwd->n[a] != inv->n[a];
-	if (differs && fwd->has_block && inv->has_block) return fail(-2, "%s: different forward / inverse extents (a rescaled block grid, motion -s) are not implemented on packed pixels", what);
-	if (!block_roundtrip_ok(fwd, inv))
-		return fail(-2, "%s needs the plan pair of the fused block pass: matching REDFT10 / REDFT01 small-block plans (every extent 4, 8 or 16, 2-D blocks up to 32; per-frame and single-block plans have no block pass)", what);
-	if (3u & ((uintptr_t)d_in | (uintptr_t)d_out)) return fail(-2, "%s: the buffers must be 4-byte aligned", what);
-	BlockPackedArgs a;
-	memset((void *)&a, 0, sizeof a);
-	static_cast<BlockGeom &>(a) = fwd->blk;
-	const BlockGeom &o = inv->blk;
-	a.sy_out = o.sy_out; a.sz_out = o.sz_out; a.sxb_out = o.sxb_out;
-	for (int d = 0; d < o.nd; d++) a.bos[d] = o.bos[d];
-	// the plans count pixels; the kernel addresses bytes
-	a.sy_in *= C; a.sz_in *= C; a.sxb_in *= C; a.sy_out *= C; a.sz_out *= C; a.sxb_out *= C;
-	long long nwg = 1;
-	for (int d = 0; d < a.nd; d++) { a.bis[d] *= C; a.bos[d] *= C; nwg *= a.bn[d]; }
-	int G = packed_group_of(a.nx, a.ny, a.nz, C, a.nxb);
-	if (const char *e = getenv("DSPFFT_PACKED_G")) { if (atoi(e) > 0) G = std::min(atoi(e), a.nxb); }      // experiments (tools/bench_motion_packed.py)
-	const size_t block_bytes = (size_t)a.nz * a.ny * C * a.nx * sizeof(float);
-	if (block_bytes + sizeof(TrcU8Tab) + 16 > 64 * 1024)
-		return fail(-2, "%s: the %d component tiles of a %dx%dx%d block (%zu bytes) and the tables do not fit a workgroup's 64 KB of LDS", what, C, a.nx, a.ny, a.nz, block_bytes);
-	while (G > 1 && (size_t)G * block_bytes + sizeof(TrcU8Tab) + 16 > 64 * 1024) G--;
-	a.G = G; a.pitch = G * C * a.nx; a.ngroups = (a.nxb + G - 1) / G; a.gdiv = make_div((uint32_t)a.ngroups);
-	nwg *= a.ngroups;
-	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch (more than 2^31 - 1 workgroups)", what);
-	a.in8 = d_in; a.out8 = d_out; a.mul8 = out_mul;
-	block_scales(fwd, a.f); block_scales(inv, a.i);
-	a.comps = C;
-	if (fp) {
-		motion_filter_of(*fp, a.filt);
-		for (int c = 0; c < C; c++) { a.damp[c] = packed->damp[c]; a.boost[c] = packed->boost[c]; a.grey_add[c] = packed->grey_add[c]; }
-		a.coded = d_coeffs_coded;
-	}
-	// --coeff-limit: at or above the block's count nothing is dropped (motion.c:654-657) and the call is the plain one
-	a.keep = cl && cl->keep < (size_t)a.nx * a.ny * a.nz ? (unsigned int)cl->keep : 0;
-	if (fwd->u8_trc) a.tab_in = (const TrcU8Tab *)fwd->u8_tab;
-	if (inv->u8_trc) { a.tab_out = (const TrcU8Tab *)inv->u8_tab; a.trc_out = inv->u8_trc; }
-	if (!dspfft_block_packed_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_packed.hip)", what);
-	if (int rc = dspfft_block_packed_launch(&a, (int)nwg, (size_t)G * block_bytes, stream)) return fail(-4, "kernel launch failed (%s): backend code %d", what, rc);
-	return 0;
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", kPacked);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", kPacked);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", kPacked);
+	if (cl && !cl->keep) return fail(-1, "%s: coefficient limit: keep must be at least 1 (pass NULL for no limit)", kPacked);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.coded = d_coeffs_coded; c.stream = stream;
+	if (cl) c.keep = cl->keep;
+	return roundtrip_core(c);
 }
 
 extern "C" int dspfft_scan_zigzag_frame_ids(uint32_t *d_ids, uint32_t w, uint32_t h, uint64_t step, void *s)
@@ -2894,7 +2892,8 @@ static bool many_pair_check(const dspfft_plan *plans, const void *const *d_in, v
 	// what dspfft_execute would run must be the plans' plain pass lists, which are what the roundtrip runs
 	if (fwd->has_block || inv->has_block || &pick_passes(fwd, d_in[i], d_out[i]) != &fwd->passes || &pick_passes(inv, d_in[i + 1], d_out[i + 1]) != &inv->passes) return false;
 	if (fwd->passes.empty() || inv->passes.empty()) return false;
-	c = RtCall{fwd, inv, (const float *)d_in[i], (float *)d_out[i], nullptr, nullptr, 1.0, nullptr, nullptr, streams ? streams[i] : nullptr, 0, nullptr, 0};
+	c = RtCall{};
+	c.fwd = fwd; c.inv = inv; c.d_in = (const float *)d_in[i]; c.d_out = (float *)d_out[i]; c.stream = streams ? streams[i] : nullptr;
 	char err[sizeof g_err];
 	memcpy(err, g_err, sizeof err);                  // a pair that is none is no error of the batch
 	const bool ok = rt_check(c) == 0 && !c.grid && !c.temporal && !c.block && !c.rescale;

@@ -181,6 +181,13 @@ class Plan:
         fp.preserve_dc = filter.get("preserve_dc", 0); fp.grey_add = filter.get("grey_add", 0.0); fp.quantizer = filter.get("quantizer", 0.0)
         return fp
 
+    @classmethod
+    def _tail(cls, filter, d_coded, stream, *between):
+        """the trailing arguments of a roundtrip or spectrogram entry: (fp, *between, d_coeffs_coded, stream); the by-reference fp keeps its
+        structure alive"""
+        fp = cls._filter_params(filter)
+        return (C.byref(fp) if fp is not None else None,) + between + (C.c_void_p(d_coded or None), C.c_void_p(stream))
+
     def _topn_work(self, inv, topn_work):
         """(pointer, bytes) of the selection's scratch: the caller's uint8 device tensor, or one allocated here when the plans need any"""
         if topn_work is None:
@@ -198,14 +205,12 @@ class Plan:
         (dspfft_execute_roundtrip_topn; 0: none); topn_work: a uint8 device tensor of dspfft_roundtrip_topn_work_bytes, allocated per
         call when None and the plans need one."""
         d_out = d_in if d_out is None else d_out
-        fp = self._filter_params(filter)
-        fpp = C.byref(fp) if fp is not None else None
         if not coeff_limit:
-            self._check(self._lib.dspfft_execute_roundtrip(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), fpp, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+            self._check(self._lib.dspfft_execute_roundtrip(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), *self._tail(filter, d_coded, stream)))
             return
         wp, wb, _hold = self._topn_work(inv, topn_work)
-        self._check(self._lib.dspfft_execute_roundtrip_topn(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), fpp, int(coeff_limit), wp, wb,
-                                                            C.c_void_p(d_coded or None), C.c_void_p(stream)))
+        self._check(self._lib.dspfft_execute_roundtrip_topn(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out),
+                                                            *self._tail(filter, d_coded, stream, int(coeff_limit), wp, wb)))
 
     def roundtrip_u8(self, inv, d_in_u8, d_out_u8, d_work, out_mul, filter=None, d_coded=0, stream=0, coeff_limit=0, topn_work=None):
         """the same with motion's 8-bit samples at both ends (motion.c:617-640, :760-776): u8 in, float work buffer, u8 out =
@@ -213,19 +218,17 @@ class Plan:
         coeff_limit, topn_work: as roundtrip's (dspfft_execute_roundtrip_u8_topn).  d_work may be None / 0 for a rescaled block grid
         (motion_grid_plans: one kernel from the input volume to the output volume, no float intermediate) and for blocks along time
         (motion_temporal_plans, likewise); every other pair needs it."""
-        fp = self._filter_params(filter)
-        fpp = C.byref(fp) if fp is not None else None
         if not coeff_limit:
             self._check(self._lib.dspfft_execute_roundtrip_u8(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
-                                                              fpp, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+                                                              *self._tail(filter, d_coded, stream)))
             return
         wp, wb, _hold = self._topn_work(inv, topn_work)
         self._check(self._lib.dspfft_execute_roundtrip_u8_topn(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
-                                                               fpp, int(coeff_limit), wp, wb, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+                                                               *self._tail(filter, d_coded, stream, int(coeff_limit), wp, wb)))
 
-    def _coeff_limit(self, inv, coeff_limit, outside_mul, topn_work):
-        """dspfft_coeff_limit for a call (and what keeps its work buffer alive)"""
-        wp, wb, hold = self._topn_work(inv, topn_work)
+    def _coeff_limit(self, inv, coeff_limit, outside_mul=1.0, topn_work=None, work=True):
+        """dspfft_coeff_limit for a call (and what keeps its work buffer alive); work=False: the call needs no work buffer"""
+        wp, wb, hold = self._topn_work(inv, topn_work) if work else (None, 0, None)
         cl = _lib.CoeffLimit()
         cl.keep = int(coeff_limit); cl.outside_mul = float(outside_mul); cl.d_work = wp.value if wp is not None else None; cl.work_bytes = wb
         return cl, hold
@@ -235,48 +238,38 @@ class Plan:
         bytes, and a rescaled block grid (motion_grid_plans; outside_mul = info["limit_outside_mul"]), whose selection ranks the whole
         max(block, scaled) embedding as the reference does.  coeff_limit must be at least 1."""
         d_out = d_in if d_out is None else d_out
-        fp = self._filter_params(filter)
         cl, _hold = self._coeff_limit(inv, coeff_limit, outside_mul, topn_work)
-        self._check(self._lib.dspfft_execute_roundtrip_limit(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), C.byref(fp) if fp is not None else None,
-                                                             C.byref(cl), C.c_void_p(d_coded or None), C.c_void_p(stream)))
+        self._check(self._lib.dspfft_execute_roundtrip_limit(self._h, inv._h, C.c_void_p(d_in), C.c_void_p(d_out), *self._tail(filter, d_coded, stream, C.byref(cl))))
 
     def roundtrip_u8_limit(self, inv, d_in_u8, d_out_u8, d_work, out_mul, coeff_limit=0, outside_mul=1.0, filter=None, d_coded=0, stream=0, topn_work=None):
         """roundtrip_u8 with motion --coeff-limit through dspfft_execute_roundtrip_u8_limit (see roundtrip_limit); d_work may be None / 0 for
         a rescaled block grid"""
-        fp = self._filter_params(filter)
         cl, _hold = self._coeff_limit(inv, coeff_limit, outside_mul, topn_work)
         self._check(self._lib.dspfft_execute_roundtrip_u8_limit(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work), out_mul,
-                                                                C.byref(fp) if fp is not None else None, C.byref(cl), C.c_void_p(d_coded or None), C.c_void_p(stream)))
+                                                                *self._tail(filter, d_coded, stream, C.byref(cl))))
 
     def roundtrip_u8_packed(self, inv, d_in_u8, d_out_u8, out_mul, packed, filter=None, coeff_limit=0, d_coded=0, stream=0):
         """dspfft_execute_roundtrip_u8_packed: the fused small-block roundtrip on packed 8-bit pixels (rgb24, rgba ...).  self / inv: the planar
         small-block pair (motion_grid_plans(shape, block, block)), planned over the clip in pixels; the buffers hold packed.components bytes per
         pixel.  packed: motion_packed(...) -- its damp, boost and grey_add (by byte position) replace the filter's; filter: as roundtrip_u8's,
         or None.  coeff_limit: motion --coeff-limit per component block (0: none).  Needs no work buffer; may run in place."""
-        fp = self._filter_params(filter)
-        cl = None
-        if coeff_limit:
-            cl = _lib.CoeffLimit()
-            cl.keep = int(coeff_limit); cl.outside_mul = 1.0; cl.d_work = None; cl.work_bytes = 0
+        cl = self._coeff_limit(inv, coeff_limit, work=False)[0] if coeff_limit else None
+        between = (C.byref(packed) if packed is not None else None, C.byref(cl) if cl is not None else None)
         self._check(self._lib.dspfft_execute_roundtrip_u8_packed(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
-                                                                 C.byref(fp) if fp is not None else None, C.byref(packed) if packed is not None else None,
-                                                                 C.byref(cl) if cl is not None else None, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+                                                                 *self._tail(filter, d_coded, stream, *between)))
 
     def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0,
                             coeff_limit=0, outside_mul=1.0, topn_work=None):
         """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
         Floyd-Steinberg dithered store of them (pel = value * scalefactor * normalization * normalization), plane by plane over inv's extents.
         coeff_limit (0: none), outside_mul, topn_work: motion --coeff-limit as roundtrip_limit's (dspfft_execute_roundtrip_u8_dither_limit)"""
-        fp = self._filter_params(filter)
         if coeff_limit:
             cl, _hold = self._coeff_limit(inv, coeff_limit, outside_mul, topn_work)
             self._check(self._lib.dspfft_execute_roundtrip_u8_dither_limit(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work),
-                                                                           float(scalefactor), float(normalization), C.byref(fp) if fp is not None else None,
-                                                                           C.byref(cl), C.c_void_p(d_coded or None), C.c_void_p(stream)))
+                                                                           float(scalefactor), float(normalization), *self._tail(filter, d_coded, stream, C.byref(cl))))
             return
         self._check(self._lib.dspfft_execute_roundtrip_u8_dither(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work),
-                                                                 float(scalefactor), float(normalization), C.byref(fp) if fp is not None else None,
-                                                                 C.c_void_p(d_coded or None), C.c_void_p(stream)))
+                                                                 float(scalefactor), float(normalization), *self._tail(filter, d_coded, stream)))
 
     def spectrogram(self, d_in, d_out, mode, scalefactor, normalization, c=None, d_work=0, filter=None, d_coded=0, stream=0, pixels="u8"):
         """motion --spectrogram (dspfft_execute_spectrogram_u8 / _f32): load -> self (REDFT10 with motion's index-0 factors) -> filter ->
@@ -284,21 +277,17 @@ class Plan:
         mode: "abs", "shift", "flat" or "copy" (or DSPFFT_MOTION_*).  c: shift's constant (motion.c:568; motion_spec_constants gives it),
         None for the other modes -- abs derives its own per block on the device.  pixels: "u8", or "f32" for motion's float pixels."""
         sp = _spec_params(mode, scalefactor, normalization, c)
-        fp = self._filter_params(filter)
         run = {"u8": self._lib.dspfft_execute_spectrogram_u8, "f32": self._lib.dspfft_execute_spectrogram_f32}[pixels]
-        self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), C.byref(fp) if fp is not None else None,
-                        C.c_void_p(d_coded or None), C.c_void_p(stream)))
+        self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), *self._tail(filter, d_coded, stream)))
 
     def ispectrogram(self, d_in, d_out, mode, scalefactor, normalization, c=None, d_work=0, filter=None, d_coded=0, stream=0, pixels="u8", out_mul=None):
         """motion --ispectrogram (dspfft_execute_ispectrogram_u8 / _f32): load -> decode -> filter -> self (REDFT01 with motion.c:751's
         factors and the global scale) -> store.  mode: "shift", "flat" or "copy"; c: shift's ic (motion.c:569).  out_mul: roundtrip_u8's,
         scalefactor normalization^2 by default."""
         sp = _spec_params(mode, scalefactor, normalization, c)
-        fp = self._filter_params(filter)
         mul = float(scalefactor) * float(normalization) ** 2 if out_mul is None else float(out_mul)
         run = {"u8": self._lib.dspfft_execute_ispectrogram_u8, "f32": self._lib.dspfft_execute_ispectrogram_f32}[pixels]
-        self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), C.byref(fp) if fp is not None else None,
-                        mul, C.c_void_p(d_coded or None), C.c_void_p(stream)))
+        self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), *self._tail(filter, d_coded, stream, mul)))
 
     def spec_u8(self, d_in, d_out, d_work, params, d_signmap=0, d_dc=0, stream=0):
         """spec on an 8-bit image in device memory (dspfft_execute_spec_u8): bytes -> self (the forward plan of spec_image_plans) -> display
@@ -592,9 +581,7 @@ def _spec_blocks(fn, d_a, d_b, n, minbuf_hw, nblocks, block_stride, mode, scalef
     hw = (n[1], n[2]) if minbuf_hw is None else minbuf_hw
     stride = hw[0] * hw[1] * n[0] if block_stride is None else int(block_stride)
     sp = _spec_params(mode, scalefactor, normalization, c)
-    fp = Plan._filter_params(filter)
-    if getattr(lib, fn)(_ptr(d_a), _ptr(d_b), _ia(n), _ia(hw), int(nblocks), stride, C.byref(sp), C.byref(fp) if fp is not None else None,
-                        C.c_void_p(d_coded or None), C.c_void_p(stream)):
+    if getattr(lib, fn)(_ptr(d_a), _ptr(d_b), _ia(n), _ia(hw), int(nblocks), stride, C.byref(sp), *Plan._tail(filter, d_coded, stream)):
         raise DspfftError(lib.dspfft_motion_last_error().decode())
 
 
