@@ -23,6 +23,8 @@ SYMBOLS = [
     "dspfft_roundtrip_topn_work_bytes", "dspfft_execute_roundtrip_topn", "dspfft_execute_roundtrip_u8_topn", "dspfft_motion_topn_blocks_work_bytes", "dspfft_motion_topn_blocks",
     "dspfft_execute_roundtrip_limit", "dspfft_execute_roundtrip_u8_limit", "dspfft_execute_roundtrip_u8_dither_limit",
     "dspfft_execute_roundtrip_u8_packed",
+    "dspfft_execute_spectrogram_u8_packed", "dspfft_execute_ispectrogram_u8_packed", "dspfft_motion_spec_blocks_u8_packed", "dspfft_motion_ispec_blocks_u8_packed",
+    "dspfft_plan_guru_r2r_ordered",
     "dspfft_execute","dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
     "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_many_fused_pairs", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_execute_n", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
     "dspfft_last_error", "dspfft_version", "dspfft_set_thread_plan_effort", "dspfft_get_thread_plan_effort", "dspfft_fftw_sparse_uploads",
@@ -159,6 +161,14 @@ def bind(lib):
         spp, fpp = C.POINTER(MotionSpecParams), C.POINTER(MotionFilterParams)
         lib.dspfft_execute_spectrogram_u8.argtypes = lib.dspfft_execute_spectrogram_f32.argtypes = [vp, vp, vp, vp, spp, fpp, vp, vp]
         lib.dspfft_execute_ispectrogram_u8.argtypes = lib.dspfft_execute_ispectrogram_f32.argtypes = [vp, vp, vp, vp, spp, fpp, C.c_double, vp, vp]
+    if hasattr(lib, "dspfft_execute_spectrogram_u8_packed"):     # (likewise)
+        spp, fpp, pkp = C.POINTER(MotionSpecParams), C.POINTER(MotionFilterParams), C.POINTER(MotionPacked)
+        lib.dspfft_plan_guru_r2r_ordered.argtypes = lib.dspfft_plan_guru_r2r.argtypes
+        lib.dspfft_execute_spectrogram_u8_packed.argtypes = [vp, vp, vp, vp, spp, fpp, pkp, vp, vp]
+        lib.dspfft_execute_ispectrogram_u8_packed.argtypes = [vp, vp, vp, vp, spp, fpp, pkp, C.c_double, vp, vp]
+    if hasattr(lib, "dspfft_motion_spec_blocks_u8_packed"):      # (the HIP-only stand-alone kernels: absent from the CPU emulation library)
+        for f in ("dspfft_motion_spec_blocks_u8_packed", "dspfft_motion_ispec_blocks_u8_packed"):
+            getattr(lib, f).argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(MotionSpecParams), C.POINTER(MotionFilterParams), C.POINTER(MotionPacked), vp, vp]
     if hasattr(lib, "dspfft_execute_spec_u8"):     # (likewise)
         ipp = C.POINTER(SpecImageParams)
         lib.dspfft_execute_spec_u8.argtypes = [vp, vp, vp, vp, vp, vp, ipp, vp]

@@ -33,6 +33,7 @@
 #include "block_packed_core.h"
 #include "temporal_core.h"
 #include "block_spec_core.h"
+#include "block_spec_packed_core.h"
 #include "trc_u8_core.h"
 #include "spec_image_core.h"
 
@@ -80,6 +81,11 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_spec_lau
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_blocks_launch(int inverse, int u8, void *d_pix, void *d_coeffs, const int n[3], const int minbuf_hw[2], size_t nblocks,
                                                                                       long long block_stride, const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter,
                                                                                       unsigned long long *d_coeffs_coded, void *stream);
+// block_spec_packed.hip's and motion_spec_packed.hip's launchers behind dspfft_execute_spectrogram_u8_packed / _ispectrogram_u8_packed.  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_spec_packed_launch(const dspfft::BlockSpecPackedArgs *a, int inverse, int nwg, size_t lds, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_frames_packed_launch(int inverse, uint8_t *d_pix, float *d_coeffs, int h, int w, int components, size_t frames,
+                                                                                       const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter,
+                                                                                       const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_row_u8_trc_launch(int row_spec_id, const dspfft::PassArgs *a, const dspfft::U8IOTrc *io, int nwg, void *stream);
 // spec_image.hip's two sweeps and spec_inst_row_u8c.hip's interleaved 8-bit row ends behind dspfft_execute_spec_u8 / _ispec_u8.  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_image_encode_launch(const dspfft::SpecImageEnc *a, void *stream);
@@ -1162,8 +1168,8 @@ extern "C" int dspfft_plan_many_r2r_f64(dspfft_plan *plan, int rank, const int *
 
 // FFTW's guru interface shape (fftw_plan_guru_r2r): every transformed and every batch dimension has its own extent and
 // input / output strides, so e.g. all 8x8x8 blocks of a volume (motion --blocksize 8x8x8) are ONE plan
-extern "C" int dspfft_plan_guru_r2r(dspfft_plan *plan, int rank, const dspfft_iodim *dims, int howmany_rank, const dspfft_iodim *howmany_dims,
-                                    const int *kinds, int f64)
+static int plan_guru(dspfft_plan *plan, int rank, const dspfft_iodim *dims, int howmany_rank, const dspfft_iodim *howmany_dims, const int *kinds, int f64,
+                     bool first_axis_first)
 {
 	if (!plan) return fail(-1, "null plan pointer");
 	*plan = nullptr;
@@ -1182,7 +1188,18 @@ extern "C" int dspfft_plan_guru_r2r(dspfft_plan *plan, int rank, const dspfft_io
 		pl->axes[a].n = dims[a].n; pl->axes[a].is = dims[a].is; pl->axes[a].os = dims[a].os;
 	}
 	for (int b = 0; b < howmany_rank; b++) if (howmany_dims[b].n > 1) pl->batches.push_back(Dim{howmany_dims[b].n, howmany_dims[b].is, howmany_dims[b].os});
-	return plan_finish(pl, plan, false);
+	return plan_finish(pl, plan, first_axis_first);
+}
+extern "C" int dspfft_plan_guru_r2r(dspfft_plan *plan, int rank, const dspfft_iodim *dims, int howmany_rank, const dspfft_iodim *howmany_dims,
+                                    const int *kinds, int f64)
+{
+	return plan_guru(plan, rank, dims, howmany_rank, howmany_dims, kinds, f64, false);
+}
+// ... with the pass order of dspfft_plan_many_r2r_ordered (f32): first_axis_first runs axis 0 first and the last axis last
+extern "C" int dspfft_plan_guru_r2r_ordered(dspfft_plan *plan, int rank, const dspfft_iodim *dims, int howmany_rank, const dspfft_iodim *howmany_dims,
+                                            const int *kinds, int first_axis_first)
+{
+	return plan_guru(plan, rank, dims, howmany_rank, howmany_dims, kinds, 0, first_axis_first != 0);
 }
 
 extern "C" int dspfft_plan_many_r2r_ordered(dspfft_plan *plan, int rank, const int *n, int howmany,
@@ -2655,6 +2672,143 @@ extern "C" int dspfft_execute_ispectrogram_f32(dspfft_plan inv, const float *d_i
                                                const dspfft_motion_filter_params *fp, double out_mul, unsigned long long *d_coeffs_coded, void *stream)
 {
 	return spec_core(SpecCall{inv, true, false, d_in, d_out, d_work, sp, fp, out_mul, d_coeffs_coded, stream});
+}
+
+// ---- motion --spectrogram / --ispectrogram on packed 8-bit pixels (rgb24, rgba ...; include/dspfft.h): two plan families, told apart by the plan ----
+namespace {
+struct SpecPackedCall {
+	dspfft_plan pl; bool inverse;
+	const uint8_t *d_in; uint8_t *d_out; float *d_work;
+	const dspfft_motion_spec_params *sp; const dspfft_motion_filter_params *fp; const dspfft_motion_packed *packed; double out_mul;
+	unsigned long long *coded; void *stream;
+};
+const char *spec_packed_name(const SpecPackedCall &c) { return c.inverse ? "ispectrogram on packed 8-bit pixels" : "spectrogram on packed 8-bit pixels"; }
+
+// (A) small blocks: the PLANAR small-block plan's geometry with every stride and offset times `components`, block_spec_packed.hip's kernel
+int spec_packed_block(const SpecPackedCall &c, const MotionFilter &mf)
+{
+	const dspfft_plan pl = c.pl;
+	const char *const what = spec_packed_name(c);
+	const int C = c.packed->components;
+	if ((3u & (uintptr_t)c.d_in) || (3u & (uintptr_t)c.d_out)) return fail(-2, "%s over small blocks: the buffers must be 4-byte aligned", what);
+	BlockSpecPackedArgs a;
+	memset((void *)&a, 0, sizeof a);
+	static_cast<BlockGeom &>(a) = pl->blk;
+	a.in8 = c.d_in; a.out8 = c.d_out; a.mul8 = c.out_mul;
+	block_scales(pl, c.inverse ? a.i : a.f);
+	a.filt = mf; a.coded = c.coded;
+	a.sp = MotionSpec{c.sp->mode, c.sp->scalefactor, c.sp->normalization, c.sp->c};
+	// the plan counts pixels; the kernel addresses bytes
+	a.sy_in *= C; a.sz_in *= C; a.sxb_in *= C; a.sy_out *= C; a.sz_out *= C; a.sxb_out *= C;
+	long long nwg = 1;
+	for (int d = 0; d < a.nd; d++) { a.bis[d] *= C; a.bos[d] *= C; nwg *= a.bn[d]; }
+	const size_t block_bytes = (size_t)a.nz * a.ny * C * a.nx * sizeof(float);
+	const int G = rt_lds_group(packed_group_of(a.nx, a.ny, a.nz, C, a.nxb), block_bytes);
+	if (!G) return fail(-2, "%s: the %d component tiles of a %dx%dx%d block (%zu bytes) do not fit a workgroup's 64 KB of LDS", what, C, a.nx, a.ny, a.nz, block_bytes);
+	a.G = G; a.pitch = G * C * a.nx; a.ngroups = (a.nxb + G - 1) / G; a.gdiv = make_div((uint32_t)a.ngroups);
+	nwg *= a.ngroups;
+	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch (more than 2^31 - 1 workgroups)", what);
+	a.comps = C;
+	if (c.fp) for (int k = 0; k < C; k++) { a.damp[k] = c.packed->damp[k]; a.boost[k] = c.packed->boost[k]; a.grey_add[k] = c.packed->grey_add[k]; }
+	if (!dspfft_block_spec_packed_launch) return fail(-3, "%s over small blocks: not built into this library (the kernels are HIP-only, block_spec_packed.hip)", what);
+	if (int rc = dspfft_block_spec_packed_launch(&a, c.inverse, (int)nwg, (size_t)G * block_bytes, c.stream)) return fail(-4, "kernel launch failed (%s over small blocks): backend code %d", what, rc);
+	return 0;
+}
+
+// (B) full frames (motion's default -b 0x0x1): the caller's in-place, dense, interleaved plan of rank 2 over [F][H][W][C] -- its passes in
+// d_work, the first (last) with the interleaved 8-bit row end where it has one, and motion_spec_packed.hip's kernel once over all frames at
+// the encoded end.  The call is the composition dspfft_u8_to_f32 -> dspfft_execute -> dspfft_motion_spec_blocks_u8_packed, and its mirror.
+int spec_packed_frames(const SpecPackedCall &c)
+{
+	const dspfft_plan pl = c.pl;
+	const char *const what = spec_packed_name(c);
+	const int C = c.packed->components;
+	if (pl->rank == 3) return fail(-2, "%s: one 3-D block of interleaved pixels (motion -b 0x0x0) is not implemented", what);
+	if (!c.d_work) return fail(-1, "%s: this plan needs the float work buffer", what);
+	const char *const layout = "the plan must be the dense in-place layout [frames][h][w][components]: rank 2, axis strides w * components and components, batch levels {components: stride 1} and {frames: stride h * w * components}";
+	if (pl->rank != 2) return fail(-2, "%s: %s", what, layout);
+	const int h = pl->n[0], w = pl->n[1];
+	const Dim *chan = nullptr;
+	for (const Dim &b : pl->batches) if (b.n > 1 && b.is == 1 && b.os == 1 && !chan) chan = &b;
+	if (!chan || chan->n != C) return fail(-2, "%s: the plan's unit-stride batch level counts %d, not the %d components of a pixel", what, chan ? chan->n : 0, C);
+	const long long frame = (long long)h * w * C;
+	long long frames = 1;
+	int levels = 0;
+	for (const Dim &b : pl->batches) {
+		if (b.n == 1 || &b == chan) continue;
+		if (levels++ || b.is != frame || b.os != frame) return fail(-2, "%s: %s", what, layout);
+		frames = b.n;
+	}
+	if (pl->axes[1].is != C || pl->axes[1].os != C || pl->axes[0].is != (long long)w * C || pl->axes[0].os != (long long)w * C) return fail(-2, "%s: %s", what, layout);
+	if (frame >= (1LL << 32)) return fail(-2, "%s: a frame of 2^32 samples or more", what);
+	if (!dspfft_spec_frames_packed_launch) return fail(-3, "%s: not built into this library (the kernels are HIP-only, motion_spec_packed.hip)", what);
+
+	float *const wk = c.d_work;
+	const uint64_t len = (uint64_t)frames * (uint64_t)frame;
+	const std::vector<Pass> &passes = pick_passes(pl, wk, wk);
+	const size_t np = passes.size();
+	// the 8-bit end on the transform's side rides on the row pass where the plain passes run, the pass has the interleaved kernel and every
+	// line of bytes starts at a multiple of 4
+	const uint8_t *const bytes = c.inverse ? c.d_out : c.d_in;
+	const bool dwords = !(3u & (uintptr_t)bytes) && ((long long)w * C) % 4 == 0;
+	const bool fused8 = &passes == &pl->passes && np >= 2 && dwords && pass_has_u8(pl, passes[c.inverse ? np - 1 : 0], true);
+	auto frames_kernel = [&](uint8_t *pix) {
+		if (dspfft_spec_frames_packed_launch(c.inverse, pix, wk, h, w, C, (size_t)frames, c.sp, c.fp, c.packed, c.coded, c.stream))
+			return fail(-4, "%s: %s", what, dspfft_motion_last_error ? dspfft_motion_last_error() : "launch failed");
+		return 0;
+	};
+	if (!c.inverse) {
+		if (fused8) {
+			if (int rc = run_pass_u8(pl, passes[0], wk, U8IO{c.d_in, nullptr, 1.0}, U8Trc(), c.stream)) return rc;
+			for (size_t i = 1; i < np; i++) if (int rc = run_pass<float>(pl, passes[i], (const float *)wk, wk, i + 1 == np, c.stream)) return rc;
+		} else {
+			if (be_u8_to_f32(wk, c.d_in, len, c.stream)) return fail(-4, "launch failed");
+			if (int rc = execute_t<float>(pl, wk, wk, c.stream)) return rc;
+		}
+		return frames_kernel(c.d_out);
+	}
+	if (int rc = frames_kernel((uint8_t *)c.d_in)) return rc;
+	if (fused8) {
+		for (size_t i = 0; i + 1 < np; i++) if (int rc = run_pass<float>(pl, passes[i], (const float *)wk, wk, false, c.stream)) return rc;
+		return run_pass_u8(pl, passes[np - 1], wk, U8IO{nullptr, c.d_out, c.out_mul}, U8Trc(), c.stream);
+	}
+	if (int rc = execute_t<float>(pl, wk, wk, c.stream)) return rc;
+	return be_f32_to_u8(c.d_out, wk, c.out_mul, len, c.stream) ? fail(-4, "launch failed") : 0;
+}
+
+// every rejection of this function and of the two above comes before the first launch
+int spec_packed_core(const SpecPackedCall &c)
+{
+	const dspfft_plan pl = c.pl;
+	const char *const what = spec_packed_name(c);
+	if (!pl || !c.d_in || !c.d_out || !c.sp) return fail(-1, "%s: null plan, buffer or parameters", what);
+	if (!c.packed) return fail(-1, "%s: null dspfft_motion_packed", what);
+	const int C = c.packed->components;
+	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
+	if (pl->f64) return fail(-2, "%s: f64 plans are not implemented", what);
+	if (pl->u8_trc) return fail(-2, "%s: a plan with a transfer characteristic (dspfft_plan_set_u8_trc) is not implemented", what);
+	const int m = c.sp->mode;
+	if (c.inverse && m == DSPFFT_MOTION_ABS) return fail(-2, "%s: the reference has no abs type (motion.c:627-630): shift, flat or copy", what);
+	if (m != DSPFFT_MOTION_ABS && m != DSPFFT_MOTION_SHIFT && m != DSPFFT_MOTION_FLAT && m != DSPFFT_MOTION_COPY) return fail(-1, "%s: mode must be %sshift, flat or copy", what, c.inverse ? "" : "abs, ");
+	for (int a = 0; a < pl->rank; a++)
+		if (pl->kinds[a] != (c.inverse ? DSPFFT_REDFT01 : DSPFFT_REDFT10)) return fail(-1, "%s: the plan must be %s on every axis", what, c.inverse ? "REDFT01" : "REDFT10");
+	MotionFilter mf;
+	if (int rc = motion_filter_of(c.fp, mf, what)) return rc;
+	if (pl->has_block) return spec_packed_block(c, mf);
+	return spec_packed_frames(c);
+}
+}  // namespace
+
+extern "C" int dspfft_execute_spectrogram_u8_packed(dspfft_plan fwd, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                                    const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *stream)
+{
+	return spec_packed_core(SpecPackedCall{fwd, false, d_in, d_out, d_work, sp, fp, packed, 1.0, d_coeffs_coded, stream});
+}
+extern "C" int dspfft_execute_ispectrogram_u8_packed(dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                                     const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed, double out_mul, unsigned long long *d_coeffs_coded,
+                                                     void *stream)
+{
+	return spec_packed_core(SpecPackedCall{inv, true, d_in, d_out, d_work, sp, fp, packed, out_mul, d_coeffs_coded, stream});
 }
 
 // ---- spec / ispec on 8-bit images (include/dspfft.h; the sweeps are spec_image.hip's, their arithmetic spec_image_core.h's) ----

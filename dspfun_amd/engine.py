@@ -64,9 +64,11 @@ class Plan:
         return cls(h, lib, dtype == "f64")
 
     @classmethod
-    def guru(cls, dims, howmany_dims, kinds, lib=None, dtype="f32"):
+    def guru(cls, dims, howmany_dims, kinds, lib=None, dtype="f32", first_axis_first=False):
         """The shape of fftw_plan_guru_r2r: dims and howmany_dims are lists of (n, in_stride, out_stride) in elements.  One plan for
-        e.g. every 8x8x8 block of a volume (motion --blocksize 8x8x8)."""
+        e.g. every 8x8x8 block of a volume (motion --blocksize 8x8x8).  first_axis_first: many_r2r's (f32 only)."""
+        if first_axis_first and dtype != "f32":
+            raise ValueError("first_axis_first is an f32 plan option")
         lib = lib or _lib.load()
         def arr(d):
             a = (_lib.IoDim * max(1, len(d)))()
@@ -74,7 +76,10 @@ class Plan:
                 a[i].n, a[i].is_, a[i].os = int(n), int(is_), int(os_)
             return a
         h = C.c_void_p()
-        rc = lib.dspfft_plan_guru_r2r(C.byref(h), len(dims), arr(dims), len(howmany_dims), arr(howmany_dims), _ia(list(kinds)), 1 if dtype == "f64" else 0)
+        if first_axis_first:
+            rc = lib.dspfft_plan_guru_r2r_ordered(C.byref(h), len(dims), arr(dims), len(howmany_dims), arr(howmany_dims), _ia(list(kinds)), 1)
+        else:
+            rc = lib.dspfft_plan_guru_r2r(C.byref(h), len(dims), arr(dims), len(howmany_dims), arr(howmany_dims), _ia(list(kinds)), 1 if dtype == "f64" else 0)
         if rc:
             raise DspfftError(lib.dspfft_last_error().decode())
         return cls(h, lib, dtype == "f64")
@@ -289,6 +294,26 @@ class Plan:
         run = {"u8": self._lib.dspfft_execute_ispectrogram_u8, "f32": self._lib.dspfft_execute_ispectrogram_f32}[pixels]
         self._check(run(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp), *self._tail(filter, d_coded, stream, mul)))
 
+    def spectrogram_packed(self, d_in, d_out, mode, scalefactor, normalization, packed, c=None, d_work=0, filter=None, d_coded=0, stream=0):
+        """motion --spectrogram on packed 8-bit pixels (dspfft_execute_spectrogram_u8_packed): spectrogram's call with packed.components
+        bytes per pixel in d_in and d_out, every component of every block a block of its own.  self: the planar small-block forward plan
+        over the clip in pixels (motion_grid_plans(shape, block, block): one kernel, no d_work), or the interleaved full-frame forward plan
+        (motion_packed_frame_plans: d_work of frames * h * w * components floats).  packed: motion_packed(...) -- its damp, boost and
+        grey_add (by byte position) replace the filter's."""
+        sp = _spec_params(mode, scalefactor, normalization, c)
+        pk = C.byref(packed) if packed is not None else None
+        self._check(self._lib.dspfft_execute_spectrogram_u8_packed(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp),
+                                                                   *self._tail(filter, d_coded, stream, pk)))
+
+    def ispectrogram_packed(self, d_in, d_out, mode, scalefactor, normalization, packed, c=None, d_work=0, filter=None, d_coded=0, stream=0, out_mul=None):
+        """motion --ispectrogram on packed 8-bit pixels (dspfft_execute_ispectrogram_u8_packed): ispectrogram's call, arguments as
+        spectrogram_packed's; self is the inverse plan of the same helpers."""
+        sp = _spec_params(mode, scalefactor, normalization, c)
+        mul = float(scalefactor) * float(normalization) ** 2 if out_mul is None else float(out_mul)
+        pk = C.byref(packed) if packed is not None else None
+        self._check(self._lib.dspfft_execute_ispectrogram_u8_packed(self._h, C.c_void_p(d_in), C.c_void_p(d_out), C.c_void_p(d_work or None), C.byref(sp),
+                                                                    *self._tail(filter, d_coded, stream, pk, mul)))
+
     def spec_u8(self, d_in, d_out, d_work, params, d_signmap=0, d_dc=0, stream=0):
         """spec on an 8-bit image in device memory (dspfft_execute_spec_u8): bytes -> self (the forward plan of spec_image_plans) -> display
         encoding -> bytes, in three sweeps.  params: spec_image_params(...).  d_signmap (abs only): also the `sign` preset's image, what
@@ -408,6 +433,28 @@ def motion_packed(pix_fmt, boost=None, damp=None, dcstop=False, normalization=1.
         p.boost[at], p.damp[at] = b[i], d[i]
         p.grey_add[at] = (1.0 - (d[i] if dcstop else b[i])) * 127.5 / (float(normalization) ** 2 * float(scalefactor))
     return p
+
+
+def motion_packed_frame_plans(frames, h, w, components, lib=None):
+    """motion's default block 0x0x1 (one full frame per block) over a clip of packed 8-bit pixels [frames][h][w][components]: the plan pair of
+    Plan.spectrogram_packed / Plan.ispectrogram_packed.  Both are in place, dense and interleaved, of rank 2 with the batch levels
+    {components: stride 1} and, for frames > 1, {frames: stride h w components}, and carry the scales motion_grid_plans gives 2-D blocks (the
+    unit z axis of the reference's 3-D plans folded in, 1 / sqrt 2 out of and sqrt 2 into index 0); inv runs its row pass last.  info:
+    scalefactor = 1, normalization, c and ic (motion_spec_constants((1, h, w))), out_mul = normalization^2."""
+    import math
+    F, h, w, comps = int(frames), int(h), int(w), int(components)
+    r2 = math.sqrt(2.0)
+    dims = [(h, w * comps, w * comps), (w, comps, comps)]
+    how = [(comps, 1, 1)] + ([(F, h * w * comps, h * w * comps)] if F > 1 else [])
+    unit = r2          # (motion_grid_plans: the unit axis of the reference's 3-D plans)
+    fwd = Plan.guru(dims, how, [REDFT10, REDFT10], lib=lib).set_scale(2 * r2 * unit)
+    inv = Plan.guru(dims, how, [REDFT01, REDFT01], lib=lib, first_axis_first=True).set_scale(unit / (2 * r2))
+    for a in range(2):
+        fwd.set_axis_scale0(a, 1.0, 1.0 / r2)
+        inv.set_axis_scale0(a, r2, 1.0)
+    k = motion_spec_constants((1, h, w))
+    info = dict(scalefactor=1.0, normalization=k["normalization"], c=k["c"], ic=k["ic"], out_mul=k["normalization"] ** 2)
+    return fwd, inv, info
 
 
 def motion_temporal_plans(shape_dhw, block_d, scaled_d=None, lib=None):
@@ -599,6 +646,29 @@ def motion_ispec_blocks(d_coeffs, d_pix, n, mode, scalefactor, normalization, c=
     """dspfft_motion_ispec_blocks_u8 / _f32: load, decode (c is ic for shift) and filter the pixels of d_pix into coefficients in d_coeffs"""
     _spec_blocks("dspfft_motion_ispec_blocks_" + pixels, d_coeffs, d_pix, n, minbuf_hw, nblocks, block_stride, mode, scalefactor, normalization, c,
                  filter, d_coded, stream, lib)
+
+
+def _spec_blocks_packed(fn, d_a, d_b, h, w, components, frames, mode, scalefactor, normalization, c, packed, filter, d_coded, stream, lib):
+    lib = lib or _lib.load()
+    sp = _spec_params(mode, scalefactor, normalization, c)
+    pk = C.byref(packed) if packed is not None else None
+    if getattr(lib, fn)(_ptr(d_a), _ptr(d_b), int(h), int(w), int(components), int(frames), C.byref(sp), *Plan._tail(filter, d_coded, stream, pk)):
+        raise DspfftError(lib.dspfft_motion_last_error().decode())
+
+
+def motion_spec_blocks_packed(d_pix, d_coeffs, h, w, components, frames, mode, scalefactor, normalization, packed, c=None, filter=None, d_coded=0,
+                              stream=0, lib=None):
+    """dspfft_motion_spec_blocks_u8_packed: filter, encode and store the coefficients of `frames` dense frames [h][w][components] in d_coeffs
+    (read only) as packed 8-bit pixels in d_pix, the same layout; every component of a frame is a block of its own (abs: its own c)."""
+    _spec_blocks_packed("dspfft_motion_spec_blocks_u8_packed", d_pix, d_coeffs, h, w, components, frames, mode, scalefactor, normalization, c, packed,
+                        filter, d_coded, stream, lib)
+
+
+def motion_ispec_blocks_packed(d_coeffs, d_pix, h, w, components, frames, mode, scalefactor, normalization, packed, c=None, filter=None, d_coded=0,
+                               stream=0, lib=None):
+    """dspfft_motion_ispec_blocks_u8_packed: load, decode (c is ic for shift) and filter the packed pixels of d_pix into d_coeffs"""
+    _spec_blocks_packed("dspfft_motion_ispec_blocks_u8_packed", d_coeffs, d_pix, h, w, components, frames, mode, scalefactor, normalization, c, packed,
+                        filter, d_coded, stream, lib)
 
 
 def _motion_linear(fn, mode, allowed, d_dst, d_src, n, minbuf_hw, extra, trc, stream, lib):

@@ -224,6 +224,9 @@ int dspfft_plan_guru_r2r(dspfft_plan *plan, int rank, const dspfft_iodim *dims, 
 int dspfft_plan_many_r2r_ordered(dspfft_plan *plan, int rank, const int *n, int howmany,
                                  const int *inembed, int istride, int idist,
                                  const int *onembed, int ostride, int odist, const int *kinds, int first_axis_first);
+/* ... and dspfft_plan_guru_r2r (f32) with that choice */
+int dspfft_plan_guru_r2r_ordered(dspfft_plan *plan, int rank, const dspfft_iodim *dims, int howmany_rank, const dspfft_iodim *howmany_dims,
+                                 const int *kinds, int first_axis_first);
 
 /* motion's transform -> filter -> inverse loop (motion/motion.c:641-753) as one call.  `fwd` is a REDFT10 plan in
  * the default order, `inv` a REDFT01 plan created with first_axis_first = 1, in place on fwd's output layout; then
@@ -472,6 +475,43 @@ int dspfft_execute_ispectrogram_u8(dspfft_plan inv, const uint8_t *d_in, uint8_t
 int dspfft_execute_ispectrogram_f32(dspfft_plan inv, const float *d_in, float *d_out, float *d_work, const dspfft_motion_spec_params *sp,
                                     const dspfft_motion_filter_params *filter, double out_mul, unsigned long long *d_coeffs_coded, void *hip_stream);
 
+/* The two 8-bit calls above on PACKED pixels -- what the reference runs them on: with --spectrogram / --ispectrogram and no -c it takes an
+ * 8-bit RGB format (motion.c:313-318), and every such format but gbrp is packed.  d_in and d_out hold packed->components (2, 3 or 4) bytes
+ * per pixel, every byte a component, and each component of each block is a block of its own (:613-615): for the transform, for the block's
+ * DC and abs's c = 255 / log1p(|dc scalefactor normalization|) (:650,755), for preserve_dc, and for d_coeffs_coded, which counts the sum
+ * over the components.  packed->damp, boost and grey_add, indexed by byte position, replace the filter's fields of those names as in
+ * dspfft_execute_roundtrip_u8_packed; filter == NULL: none, and only packed->components is read.  Modes as above (abs is refused on the
+ * inverse side).  Two plan families, told apart by the plan:
+ *   small blocks   the PLANAR small-block plan over the clip in PIXELS (the plans dspfft_execute_roundtrip_u8_packed takes: volume layout
+ *                  or block-major stack, extents 4 / 8 / 16, 2-D blocks up to 32); the call multiplies every stride and offset by
+ *                  `components`.  ONE kernel (block_spec_packed.hip): a thread reads or writes the NX * components bytes of a pixel
+ *                  block's line as whole dwords and picks the components apart in registers.  The bytes EQUAL those of the planar call
+ *                  with the same plan on each component's plane with that component's damp, boost and grey_add.  d_work is not touched
+ *                  and may be NULL; the buffers must be 4-byte aligned.
+ *   full frames    (motion's default -b 0x0x1) the caller's in-place, dense, interleaved f32 plan of rank 2 over [F][H][W][C]: axes
+ *                  {H: stride W C, W: stride C}, batch levels {C: stride 1} and, for F > 1, {F: stride H W C} (dspfft_plan_guru_r2r;
+ *                  the inverse with dspfft_plan_guru_r2r_ordered(..., 1), so that its row pass ends it).  d_work is required: F H W C
+ *                  floats, sharing the layout element for element.  spectrogram: the plan's passes into d_work -- the first with the
+ *                  interleaved 8-bit row load where the plan has one and every line of bytes starts at a multiple of 4, after
+ *                  dspfft_u8_to_f32 otherwise --, then dspfft_motion_spec_blocks_u8_packed once over all frames; ispectrogram:
+ *                  dspfft_motion_ispec_blocks_u8_packed into d_work, then the passes, the last with the 8-bit store where it has one,
+ *                  else dspfft_f32_to_u8.  The bytes EQUAL those of that composition with dspfft_execute.
+ * Both are stream-ordered, allocate nothing and allow d_in == d_out.  Nothing is launched when they fail:
+ *   -1  a NULL plan, buffer, sp or packed; a bad mode; bad filter parameters; the wrong transform kind on an axis; a full-frame plan
+ *       without d_work
+ *   -2  components outside 2..4; an f64 plan; a plan with dspfft_plan_set_u8_trc set; abs on the inverse side; small blocks: buffers off
+ *       4 bytes, a tile of `components` blocks that does not fit a workgroup's 64 KB of LDS (of the listed extents 16 x 16 x 16 at
+ *       four components), more than 2^31 - 1 workgroups; full frames: a plan whose unit-stride batch level does not count
+ *       packed->components, or that is not the dense in-place layout above; a plan of rank 3 that is no small-block plan (one 3-D
+ *       block, -b 0x0x0: a stated follow-up)
+ *   -3  a library built without the HIP kernels */
+int dspfft_execute_spectrogram_u8_packed(dspfft_plan fwd, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                         const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                         unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_execute_ispectrogram_u8_packed(dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, const dspfft_motion_spec_params *sp,
+                                          const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed, double out_mul,
+                                          unsigned long long *d_coeffs_coded, void *hip_stream);
+
 /* spec and ispec on 8-bit images (spec/spec.c:63-139 and spec/ispec.c:84-167 with an 8-bit reader and writer) as one call each way, device
  * memory to device memory:
  *   spec_u8   bytes -> REDFT10 over h x w with `channels` interleaved signals -> display encoding (dspfft_spec_encode's codes; the divisors
@@ -694,6 +734,18 @@ int dspfft_motion_ispec_blocks_u8(float *d_coeffs, const uint8_t *d_pix, const i
                                   const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
 int dspfft_motion_ispec_blocks_f32(float *d_coeffs, const float *d_pix, const int n[3], const int minbuf_hw[2], size_t nblocks, long long block_stride,
                                    const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter, unsigned long long *d_coeffs_coded, void *hip_stream);
+/* The 8-bit pair on PACKED pixels, over `frames` dense frames [h][w][components] that d_pix and d_coeffs share element for element (what
+ * dspfft_execute_spectrogram_u8_packed / _ispectrogram_u8_packed run beside the passes of a full-frame plan; motion_spec_packed.hip).  Every
+ * component of a frame is a block of its own: element e of a row belongs to component e mod components at x = e / components, abs takes a
+ * component's c from that component's DC at the frame's first pixel, and packed->damp, boost and grey_add (by byte position) replace the
+ * filter's.  A thread moves one dword of pixels and a float4 of coefficients where w * components is a multiple of 4, d_pix 4-byte and
+ * d_coeffs 16-byte aligned, one sample otherwise.  The bytes (coefficients) EQUAL those of the planar pair on each de-interleaved component
+ * with n = (1, h, w) and nblocks = frames.  sp->mode none is allowed in both, abs in spec_blocks only; components must be 2, 3 or 4 and
+ * equal packed->components.  Errors: dspfft_motion_last_error. */
+int dspfft_motion_spec_blocks_u8_packed(uint8_t *d_pix, const float *d_coeffs, int h, int w, int components, size_t frames, const dspfft_motion_spec_params *sp,
+                                        const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *hip_stream);
+int dspfft_motion_ispec_blocks_u8_packed(float *d_coeffs, const uint8_t *d_pix, int h, int w, int components, size_t frames, const dspfft_motion_spec_params *sp,
+                                         const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *hip_stream);
 /* the float-pixel pair with motion --linear, which the reference applies with --ispec / --spec none (and copy on the store) only:
  * load  pel = sample * 255 (a float product); coeff = (float)(decode(pel / 255) * 255)          (motion.c:623,633)
  * store pel = coeff * scalefactor * normalization; pel *= normalization; sample = (float)(encode(pel / 255) * 255 / 255)   (:759,767-769,774)
