@@ -5,7 +5,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include "dct_core.h"
-#include "motion_filter.h"
+#include "motion_filter_packed.h"
 #include "dct_spec.h"
 #include "dct_duo.h"
 #include "dct_czt.h"
@@ -95,6 +95,10 @@ int be_czt_tables(cf *atab, cf *etab, cf *htab, int nc, int nout, int P, double 
 int be_transpose(float *out, long long out_pitch, const float *in, long long in_pitch, int rows, int cols, void *stream);
 // fused column roundtrip: REDFT10 along the tile axis (af), pointwise filter, REDFT01 (ai); both passes share spec `id`
 int be_launch_roundtrip(int id, const PassArgs &af, const PassArgs &ai, const MotionFilter &filt, unsigned long long *coded, int nwg, void *stream);
+// ... with the filter of packed pixels over full frames (motion_filter_packed.h) for the listed column specs that have that twin
+// (spec_inst_rt_packed_a/b.hip).  Weak: the CPU emulation links the engine without those units, and the engine asks before it calls.
+__attribute__((weak)) bool be_roundtrip_packed_has(int id);
+__attribute__((weak)) int be_launch_roundtrip_packed(int id, const PassArgs &af, const PassArgs &ai, const MotionFilterPacked &filt, unsigned long long *coded, int nwg, void *stream);
 
 // strided 3-D regions between an 8-bit buffer and a float buffer (motion's block / scaled regions inside a larger embedding,
 // motion/motion.c:617-640,756-776), and zeroing (motion.c:619 memset before a block is loaded)

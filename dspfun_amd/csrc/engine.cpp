@@ -83,6 +83,8 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_blocks_la
                                                                                       unsigned long long *d_coeffs_coded, void *stream);
 // block_spec_packed.hip's and motion_spec_packed.hip's launchers behind dspfft_execute_spectrogram_u8_packed / _ispectrogram_u8_packed.  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_spec_packed_launch(const dspfft::BlockSpecPackedArgs *a, int inverse, int nwg, size_t lds, void *stream);
+extern "C" __attribute__((weak)) int dspfft_motion_filter_packed(float *d_coeffs, int h, int w, int components, size_t frames, const dspfft_motion_filter_params *filter,
+                                                                 const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *stream);   // motion_filter_packed.hip
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_spec_frames_packed_launch(int inverse, uint8_t *d_pix, float *d_coeffs, int h, int w, int components, size_t frames,
                                                                                        const dspfft_motion_spec_params *sp, const dspfft_motion_filter_params *filter,
                                                                                        const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *stream);
@@ -1834,7 +1836,8 @@ struct RtArgs {
 	double outside_mul;                   // > 0: the call came through a dspfft_execute_roundtrip*_limit entry, which takes a limit on a rescaled block grid
 	Dither dither;                        // out8 non-NULL (d_out8 NULL): the inverse ends in d_out as floats and the dither kernel stores the bytes from there
 	const dspfft_motion_packed *packed;   // non-NULL: dspfft_execute_roundtrip_u8_packed's call, d_in8 / d_out8 hold packed->components bytes per pixel
-	bool may_slice = true;                // false: a slice of a clip (roundtrip_sliced)
+	bool packed_frames;                   // ... dspfft_execute_roundtrip_u8_packed_frames's: the interleaved full-frame pair, d_out is the float work buffer
+	bool may_slice = true;               // false: a slice of a clip (roundtrip_sliced)
 };
 // ... and what rt_check derives from them for the runners (zero before)
 struct RtCall : RtArgs {
@@ -1853,6 +1856,10 @@ struct RtCall : RtArgs {
 	bool temporal;                        // blocks along time that the plans' own passes cannot run (rt_temporal): temporal_rt.hip's kernel runs the call
 	TemporalArgs tp;                      // its arguments but the tables (rt_run_temporal)
 	BlockPackedArgs pk;                   // packed pixels (rt_packed): block_packed.hip's kernel runs the call
+	MotionFilterPacked mfp;               // packed pixels over full frames (rt_packed_frames): the filter of the fused column kernel's twin,
+	dspfft_motion_filter_params pf_fp;    // ... and of the stand-alone kernel (the call's, with the frame's geometry), over
+	int pf_h, pf_w; long long pf_frames;  // ... that many frames of h x w pixels
+	bool pf_plain;                        // ... no filter, or one that is position-free and the same for every component: mf runs in the planar fused kernel
 	int nwg; size_t lds;                  // the launch of the grid's, the temporal blocks' or the packed pixels' one kernel
 };
 // the dspfft_coeff_limit of a dspfft_execute_roundtrip*_limit entry into its call: what every such entry refuses of it comes first
@@ -2100,6 +2107,28 @@ int rt_run_temporal(const RtCall &c)
 // ---- motion on packed 8-bit pixels (rgb24, rgba ...; include/dspfft.h): the planar small-block pair's geometry with every stride and offset
 // times `components`, block_packed.hip's kernel.  The entry has refused null plans, buffers and c.packed, f64 plans and a limit of 0; the rest
 // of the call is checked here, the library's own lack of the kernel last.  0: c.pk is set; < 0: the call cannot run.  Nothing is launched here.
+// Full frames of packed pixels: whether `pl` is the dense in-place interleaved plan of rank 2 over [frames][h][w][C] -- axes {h: stride w C,
+// w: stride C}, batch levels {C: stride 1} and, for frames > 1, {frames: stride h w C} -- and how many frames it counts.  -2 with the reason.
+int packed_frames_layout(const dspfft_plan_s *pl, int C, const char *what, long long &frames)
+{
+	const char *const layout = "the plan must be the dense in-place layout [frames][h][w][components]: rank 2, axis strides w * components and components, batch levels {components: stride 1} and {frames: stride h * w * components}";
+	if (pl->rank != 2) return fail(-2, "%s: %s", what, layout);
+	const int h = pl->n[0], w = pl->n[1];
+	const Dim *chan = nullptr;
+	for (const Dim &b : pl->batches) if (b.n > 1 && b.is == 1 && b.os == 1 && !chan) chan = &b;
+	if (!chan || chan->n != C) return fail(-2, "%s: the plan's unit-stride batch level counts %d, not the %d components of a pixel", what, chan ? chan->n : 0, C);
+	const long long frame = (long long)h * w * C;
+	frames = 1;
+	int levels = 0;
+	for (const Dim &b : pl->batches) {
+		if (b.n == 1 || &b == chan) continue;
+		if (levels++ || b.is != frame || b.os != frame) return fail(-2, "%s: %s", what, layout);
+		frames = b.n;
+	}
+	if (pl->axes[1].is != C || pl->axes[1].os != C || pl->axes[0].is != (long long)w * C || pl->axes[0].os != (long long)w * C) return fail(-2, "%s: %s", what, layout);
+	return 0;
+}
+
 constexpr const char *kPacked = "roundtrip on packed 8-bit pixels";
 int rt_packed(RtCall &c)
 {
@@ -2143,12 +2172,64 @@ int rt_run_packed(const RtCall &c)
 	return 0;
 }
 
+// ---- motion on packed 8-bit pixels over full frames (the reference's default -b 0x0x1; include/dspfft.h): the interleaved rank-2 pair over
+// [F][h][w][C], run by rt_run_passes with the filter of packed pixels in the middle.  The entry has refused null plans, buffers, d_work and
+// c.packed and f64 plans.  0: the call is ready for rt_run_passes; < 0: it cannot run.  Nothing is launched here.
+constexpr const char *kPackedFrames = "roundtrip on packed 8-bit pixels over full frames";
+int rt_packed_frames(RtCall &c)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const char *const what = kPackedFrames;
+	if (int rc = rt_filter(c, what)) return rc;
+	const int C = c.packed->components;
+	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
+	if (fwd->has_block || inv->has_block) return fail(-2, "%s: a small-block pair runs as one kernel without a work buffer: dspfft_execute_roundtrip_u8_packed", what);
+	if (fwd->rank == 3 || inv->rank == 3) return fail(-2, "%s: one 3-D block of interleaved pixels (motion -b 0x0x0) is not implemented", what);
+	if (extents_differ(fwd, inv)) return fail(-2, "%s: different forward / inverse extents (motion -s) are not implemented on packed pixels", what);
+	long long frames, iframes;
+	if (int rc = packed_frames_layout(fwd, C, what, frames)) return rc;
+	if (int rc = packed_frames_layout(inv, C, what, iframes)) return rc;
+	const size_t nf = fwd->passes.size(), ni = inv->passes.size();
+	bool kinds = frames == iframes && nf == 2 && ni == 2;
+	for (int a = 0; a < 2; a++) kinds = kinds && fwd->kinds[a] == DSPFFT_REDFT10 && inv->kinds[a] == DSPFFT_REDFT01;
+	if (!kinds || fwd->passes[1].axis != 0 || inv->passes[0].axis != 0)
+		return fail(-2, "%s: the pair must be REDFT10 (forward) and REDFT01 (inverse) over the same frames, the inverse running its column pass first (dspfft_plan_guru_r2r_ordered(..., 1))", what);
+	const int h = fwd->n[0], w = fwd->n[1];
+	const long long frame = (long long)h * w * C;
+	if (frame >= (1LL << 32)) return fail(-2, "%s: a frame of 2^32 samples or more", what);
+	rt_trc_ends(c);
+	if (!dspfft_motion_filter_packed || ((c.trc_in.id || c.trc_out.id) && !dspfft_u8_trc_flat_launch))
+		return fail(-3, "%s: not built into this library (the kernels are HIP-only, motion_filter_packed.hip)", what);
+
+	c.F = &fwd->passes[1]; c.I = &inv->passes[0];
+	c.span = frames * frame;
+	c.pf_h = h; c.pf_w = w; c.pf_frames = frames;
+	// an 8-bit end rides on the row pass where the pass has the interleaved kernel, every line of bytes starts at a multiple of 4 and the
+	// end has no transfer characteristic (those are the flat sweeps' alone)
+	const bool lines4 = ((long long)w * C) % 4 == 0;
+	c.u8_first = !c.trc_in.id && lines4 && !(3u & (uintptr_t)c.d_in8) && pass_has_u8(fwd, fwd->passes[0], true);
+	c.u8_last = !c.trc_out.id && lines4 && !(3u & (uintptr_t)c.d_out8) && pass_has_u8(inv, inv->passes[1], true);
+	memset((void *)&c.mfp, 0, sizeof c.mfp);
+	c.pf_plain = true;
+	if (c.fp) {
+		// active = (1, h, w): every component of a frame is a block of its own; the band and the thresholds are the call's
+		dspfft_motion_filter_params &q = c.pf_fp;
+		q = *c.fp;
+		q.active[0] = 1; q.active[1] = h; q.active[2] = w; q.minbuf_hw[0] = h; q.minbuf_hw[1] = w; q.block_depth = 1;
+		q.damp = q.boost = 1.f; q.grey_add = 0.f;                 // (what the planar kernel sees when nothing but the quantiser acts)
+		motion_filter_from(q, c.mf);
+		motion_filter_packed_set(c.mfp, c.mf, h, w, C, c.packed->damp, c.packed->boost, c.packed->grey_add);
+		c.pf_plain = c.mfp.quant_only != 0;
+	}
+	return 0;
+}
+
 // every rejection of a roundtrip call; nothing has been launched when it returns
 int rt_check(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
 	const dspfft_motion_filter_params *fp = c.fp;
-	if (c.packed) return rt_packed(c);                         // (its entry takes no other strategy, and has seen to plans and buffers)
+	if (c.packed) return c.packed_frames ? rt_packed_frames(c) : rt_packed(c);      // (their entries take no other strategy, and have seen to plans and buffers)
 	if (!fwd || !inv || !(c.d_in || c.d_in8) || !(c.d_out || c.d_out8)) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
 	if (int t = rt_temporal(c)) return t < 0 ? t : 0;          // (ahead of rt_grid, which answers every rescaled pair with batches that it is no grid)
@@ -2293,6 +2374,10 @@ bool rt_col_fused(const RtCall &c, const float *src, PassArgs &af, PassArgs &ai,
 	                     F.hostloop.empty() && I.hostloop.empty() && (15u & ((uintptr_t)src | (uintptr_t)c.d_out)) == 0 && !fused_roundtrip_off() &&
 	                     !c.keep;             // (the selection needs every coefficient of a block before the filter sees one)
 	if (!fusable) return false;
+	// packed pixels over full frames: the twin with their filter is a listed kernel's only, and addresses the clip with 31-bit offsets -- else
+	// the unfused sequence with the frame-local kernel
+	if (c.packed && c.fp && c.span >= (1ll << 31)) return false;
+	if (c.packed && !c.pf_plain && (compiled || !be_roundtrip_packed_has || !be_roundtrip_packed_has(F.spec.id))) return false;
 	fill_args(af, F.spa, fwd, F, src, c.d_out, fwd->scale, Fuse());
 	fill_args(ai, I.spa, inv, I, (const float *)c.d_out, c.d_out, inv->passes.size() == 1 ? inv->scale : 1.0, Fuse());
 	return is_plain_args(af) && is_plain_args(ai);      // (the fused kernel is the plain instantiation of both passes)
@@ -2325,11 +2410,14 @@ int rt_run_passes(const RtCall &c)
 			// parameters: (PassArgs af, PassArgs ai, FilterOp filt, unsigned long long *coded); FilterOp is the MotionFilter, nothing else
 			void *args[4] = {&af, &ai, (void *)&c.mf, (void *)&c.coded};
 			if (int rc = be_jit_launch_n(F.jit_fn_rt, args, F.spec_nwg, F.jit_nthr, stream)) return fail(-4, "kernel launch failed (fused roundtrip, compiled at plan time): backend code %d", rc);
+		} else if (c.packed && !c.pf_plain) {
+			if (int rc = be_launch_roundtrip_packed(F.spec.id, af, ai, c.mfp, c.coded, F.spec_nwg, stream)) return fail(-4, "kernel launch failed (fused roundtrip, packed pixels): backend code %d", rc);
 		} else if (int rc = be_launch_roundtrip(F.spec.id, af, ai, c.mf, c.coded, F.spec_nwg, stream)) return fail(-4, "kernel launch failed (fused roundtrip): backend code %d", rc);
 	} else {
 		if (int rc = run_pass<float>(fwd, F, src, d_out, true, stream)) return rc;
 		if (c.keep) if (int rc = rt_topn(c)) return rc;
-		if (c.fp && be_motion_filter(d_out, c.mf, (uint64_t)c.span, c.coded, stream)) return fail(-4, "filter launch failed");
+		if (c.fp && (c.packed ? dspfft_motion_filter_packed(d_out, c.pf_h, c.pf_w, c.packed->components, (size_t)c.pf_frames, &c.pf_fp, c.packed, c.coded, stream)
+		                      : be_motion_filter(d_out, c.mf, (uint64_t)c.span, c.coded, stream))) return fail(-4, "filter launch failed");
 		if (int rc = run_pass<float>(inv, I, (const float *)d_out, d_out, ni == 1, stream)) return rc;
 	}
 	for (size_t i = 1; i < ni; i++) {
@@ -2485,7 +2573,7 @@ int roundtrip_core(RtCall &c)
 {
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
-	if (c.packed) rc = rt_run_packed(c);
+	if (c.packed) rc = c.packed_frames ? rt_run_passes(c) : rt_run_packed(c);
 	else if (c.grid) rc = rt_run_grid(c);
 	else if (c.temporal) rc = rt_run_temporal(c);
 	else if (c.block) rc = rt_run_block(c);
@@ -2725,21 +2813,10 @@ int spec_packed_frames(const SpecPackedCall &c)
 	const int C = c.packed->components;
 	if (pl->rank == 3) return fail(-2, "%s: one 3-D block of interleaved pixels (motion -b 0x0x0) is not implemented", what);
 	if (!c.d_work) return fail(-1, "%s: this plan needs the float work buffer", what);
-	const char *const layout = "the plan must be the dense in-place layout [frames][h][w][components]: rank 2, axis strides w * components and components, batch levels {components: stride 1} and {frames: stride h * w * components}";
-	if (pl->rank != 2) return fail(-2, "%s: %s", what, layout);
+	long long frames;
+	if (int rc = packed_frames_layout(pl, C, what, frames)) return rc;
 	const int h = pl->n[0], w = pl->n[1];
-	const Dim *chan = nullptr;
-	for (const Dim &b : pl->batches) if (b.n > 1 && b.is == 1 && b.os == 1 && !chan) chan = &b;
-	if (!chan || chan->n != C) return fail(-2, "%s: the plan's unit-stride batch level counts %d, not the %d components of a pixel", what, chan ? chan->n : 0, C);
 	const long long frame = (long long)h * w * C;
-	long long frames = 1;
-	int levels = 0;
-	for (const Dim &b : pl->batches) {
-		if (b.n == 1 || &b == chan) continue;
-		if (levels++ || b.is != frame || b.os != frame) return fail(-2, "%s: %s", what, layout);
-		frames = b.n;
-	}
-	if (pl->axes[1].is != C || pl->axes[1].os != C || pl->axes[0].is != (long long)w * C || pl->axes[0].os != (long long)w * C) return fail(-2, "%s: %s", what, layout);
 	if (frame >= (1LL << 32)) return fail(-2, "%s: a frame of 2^32 samples or more", what);
 	if (!dspfft_spec_frames_packed_launch) return fail(-3, "%s: not built into this library (the kernels are HIP-only, motion_spec_packed.hip)", what);
 
@@ -2977,6 +3054,21 @@ extern "C" int dspfft_execute_roundtrip_u8_packed(dspfft_plan fwd, dspfft_plan i
 	RtCall c = {};
 	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.coded = d_coeffs_coded; c.stream = stream;
 	if (cl) c.keep = cl->keep;
+	return roundtrip_core(c);
+}
+
+// ... over full frames (rt_packed_frames): the interleaved pair, through rt_run_passes in d_work
+extern "C" int dspfft_execute_roundtrip_u8_packed_frames(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
+                                                         const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed,
+                                                         unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", kPackedFrames);
+	if (!d_work) return fail(-1, "%s: null float work buffer (frames * h * w * components floats)", kPackedFrames);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", kPackedFrames);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", kPackedFrames);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.d_out = d_work; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.packed_frames = true;
+	c.coded = d_coeffs_coded; c.stream = stream;
 	return roundtrip_core(c);
 }
 

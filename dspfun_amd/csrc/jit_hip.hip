@@ -36,7 +36,7 @@ std::string device_arch(int dev)
 unsigned long long source_hash(const char *incdir)
 {
 	unsigned long long h = 1469598103934665603ull;
-	for (const char *name : {"jit_kernels.h", "dct_spec.h", "dct_core.h", "radix.h", "spec_fused.h", "motion_filter.h", "elementwise_core.h", "backend.h", "trc_u8_core.h", "trc_core.h"}) {
+	for (const char *name : {"jit_kernels.h", "dct_spec.h", "dct_core.h", "radix.h", "spec_fused.h", "motion_filter.h", "motion_filter_packed.h", "elementwise_core.h", "backend.h", "trc_u8_core.h", "trc_core.h"}) {
 		FILE *f = fopen((std::string(incdir) + "/" + name).c_str(), "rb");
 		if (!f) { h ^= 0xff; h *= 1099511628211ull; continue; }
 		unsigned char buf[65536];

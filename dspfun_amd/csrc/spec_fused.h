@@ -5,7 +5,7 @@
 #ifndef DSP_STAMP
 #define DSP_STAMP(i) ((void)0)
 #endif
-#include "motion_filter.h"
+#include "motion_filter_packed.h"
 
 namespace dspfft {
 
@@ -18,6 +18,22 @@ struct FilterOp {
 		if (!p.enabled) return v;
 		float4 f; f.x = v.s[0].x; f.y = v.s[0].y; f.z = v.s[1].x; f.w = v.s[1].y;
 		f = motion_filter4(p, (uint32_t)e, f, coded);
+		v.s[0].x = f.x; v.s[0].y = f.y; v.s[1].x = f.z; v.s[1].y = f.w;
+		return v;
+	}
+};
+
+// the same over full frames of packed pixels [frames][h][w][C] (motion_filter_packed.h): the element's component picks damp, boost and grey_add.
+// A tile's groups of four lie inside a row (the tile width divides w C), but may straddle pixels.  Inlined by force: left to the inliner, the
+// tiles with seven and more calls a thread kept the operator as a function, and with it its arguments -- this structure and the count -- in
+// scratch memory.
+struct PackedFilterOp {
+	MotionFilterPacked p;
+	__device__ __forceinline__ SigVec<float, 2> operator()(long long e, SigVec<float, 2> v, unsigned long long &coded) const
+	{
+		if (!p.f.enabled) return v;
+		float4 f; f.x = v.s[0].x; f.y = v.s[0].y; f.z = v.s[1].x; f.w = v.s[1].y;
+		f = motion_filter_packed4(p, (uint32_t)e, f, coded);
 		v.s[0].x = f.x; v.s[0].y = f.y; v.s[1].x = f.z; v.s[1].y = f.w;
 		return v;
 	}
@@ -43,8 +59,8 @@ template <class PA> __host__ __device__ inline PA plain_args(const PA &a_)
 }
 template <class PA> static inline bool is_plain(const PA &a) { return !a.mask && !a.zflags && !a.accumulate && a.win_hi <= 0 && !a.alt_out && !a.in_mul && !a.in_rev; }
 
-template <class S>
-__device__ __forceinline__ void col_roundtrip_body(unsigned char *lds, const typename S::PA &af_, const typename S::PA &ai_, const FilterOp &filt, unsigned long long *coded)
+template <class S, class F>
+__device__ __forceinline__ void col_roundtrip_body(unsigned char *lds, const typename S::PA &af_, const typename S::PA &ai_, const F &filt, unsigned long long *coded)
 {
 	// motion's roundtrip is a plain pair of passes: the fused scan step's mask / flags / accumulation and zoom's window / modulation / alternating
 	// sign are pinned off (launch_col_roundtrip refuses them), so their per-load selects and the masked variants of prefetch fold away

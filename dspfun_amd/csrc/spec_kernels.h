@@ -678,6 +678,13 @@ __global__ void __launch_bounds__(S::T, rt_waves_per_simd<S>()) col_roundtrip_ke
 	extern __shared__ __attribute__((aligned(32))) unsigned char lds[];
 	col_roundtrip_body<S>(lds, af, ai, filt, coded);
 }
+// ... with the filter of packed pixels in the middle (dspfft_execute_roundtrip_u8_packed_frames; instantiated in spec_inst_rt_packed_*.hip)
+template <class S>
+__global__ void __launch_bounds__(S::T, rt_waves_per_simd<S>()) col_roundtrip_packed_kernel(const typename S::PA af, const typename S::PA ai, const PackedFilterOp filt, unsigned long long *coded)
+{
+	extern __shared__ __attribute__((aligned(32))) unsigned char lds[];
+	col_roundtrip_body<S>(lds, af, ai, filt, coded);
+}
 
 
 template <class S, int KIND>
@@ -836,6 +843,26 @@ int launch_col_roundtrip(const typename S::PA &af, const typename S::PA &ai, con
 	hipLaunchKernelGGL((col_roundtrip_kernel<S>), dim3(nwork), dim3(S::T), S::LDS, (hipStream_t)stream, af, ai, f, coded);
 	HIPCHK(hipGetLastError());
 	return 0;
+}
+template <class S>
+int launch_col_roundtrip_packed(const typename S::PA &af, const typename S::PA &ai, const MotionFilterPacked &filt, unsigned long long *coded, int nwork, void *stream)
+{
+	if (!is_plain(af) || !is_plain(ai)) return -5;
+	static DevOnce once;
+	if (int lds_rc = allow_lds_dev(once, S::LDS, col_roundtrip_packed_kernel<S>)) return lds_rc;
+	PackedFilterOp f; f.p = filt;
+	hipLaunchKernelGGL((col_roundtrip_packed_kernel<S>), dim3(nwork), dim3(S::T), S::LDS, (hipStream_t)stream, af, ai, f, coded);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+// Which listed column specs get the packed twin (spec_inst_rt_packed_a/b.hip): every one whose twin stays out of scratch memory (`make
+// check-scratch`).  The tall tiles sit at the register limit with the planar filter already (spec_fused.h); a height left out here runs the
+// call's unfused column sequence.
+constexpr bool rt_packed_listed(int n, int k, int t) { return true; }
+typedef int (*RtPackedLaunch)(const PassArgs &, const PassArgs &, const MotionFilterPacked &, unsigned long long *, int, void *);
+template <int N, int K, int T, class S> constexpr RtPackedLaunch rt_packed_launcher()
+{
+	if constexpr (rt_packed_listed(N, K, T)) return launch_col_roundtrip_packed<S>; else return nullptr;
 }
 
 }  // namespace dspfft

@@ -263,6 +263,15 @@ class Plan:
         self._check(self._lib.dspfft_execute_roundtrip_u8_packed(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
                                                                  *self._tail(filter, d_coded, stream, *between)))
 
+    def roundtrip_u8_packed_frames(self, inv, d_in_u8, d_out_u8, d_work, out_mul, packed, filter=None, d_coded=0, stream=0):
+        """dspfft_execute_roundtrip_u8_packed_frames: motion's default block 0x0x1 on packed 8-bit pixels (rgb24, rgba ...) -- every component of
+        every frame one block.  self / inv: motion_packed_frame_plans(frames, h, w, components); d_work: frames * h * w * components floats;
+        out_mul: info["out_mul"].  packed: motion_packed(...) -- its damp, boost and grey_add (by byte position) replace the filter's; filter:
+        as roundtrip_u8's (active, minbuf_hw and block_depth are the call's own: (1, h, w), (h, w), 1), or None.  May run in place."""
+        pk = C.byref(packed) if packed is not None else None
+        self._check(self._lib.dspfft_execute_roundtrip_u8_packed_frames(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work or None),
+                                                                        float(out_mul), *self._tail(filter, d_coded, stream, pk)))
+
     def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0,
                             coeff_limit=0, outside_mul=1.0, topn_work=None):
         """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
@@ -646,6 +655,16 @@ def motion_ispec_blocks(d_coeffs, d_pix, n, mode, scalefactor, normalization, c=
     """dspfft_motion_ispec_blocks_u8 / _f32: load, decode (c is ic for shift) and filter the pixels of d_pix into coefficients in d_coeffs"""
     _spec_blocks("dspfft_motion_ispec_blocks_" + pixels, d_coeffs, d_pix, n, minbuf_hw, nblocks, block_stride, mode, scalefactor, normalization, c,
                  filter, d_coded, stream, lib)
+
+
+def motion_filter_packed(d_coeffs, h, w, components, frames, packed, filter, d_coded=0, stream=0, lib=None):
+    """dspfft_motion_filter_packed: motion's filter, in place, over `frames` dense frames [h][w][components] of coefficients; every component of
+    a frame is a block of its own, filtered with packed's damp, boost and grey_add for its byte position (motion_packed(...)).  filter: the
+    dictionary of Plan.roundtrip_u8's, active = (1, h, w) for whole frames."""
+    lib = lib or _lib.load()
+    pk = C.byref(packed) if packed is not None else None
+    if lib.dspfft_motion_filter_packed(_ptr(d_coeffs), int(h), int(w), int(components), int(frames), *Plan._tail(filter, d_coded, stream, pk)):
+        raise DspfftError(lib.dspfft_motion_last_error().decode())
 
 
 def _spec_blocks_packed(fn, d_a, d_b, h, w, components, frames, mode, scalefactor, normalization, c, packed, filter, d_coded, stream, lib):

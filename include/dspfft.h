@@ -433,6 +433,40 @@ int dspfft_execute_roundtrip_u8_packed(dspfft_plan fwd, dspfft_plan inv, const u
                                        const dspfft_coeff_limit *cl /* NULL: no --coeff-limit */,
                                        unsigned long long *d_coeffs_coded, void *hip_stream);
 
+/* The same on FULL FRAMES of packed pixels -- the reference's default block -b 0x0x1, what `motion -q 20 in.png out.png` or
+ * `motion -c pixel_format=rgb24` on a clip runs: every component of every frame is one block (:613-615).  An entry of its own because the
+ * passes of full frames need a float work buffer, which the small-block entry has no argument for.
+ *   fwd, inv     the caller's in-place, dense, interleaved f32 pair of rank 2 over [F][H][W][C], the plans of the full-frame spectrogram calls
+ *                below: axes {H: stride W C, W: stride C}, batch levels {C: stride 1} and, for F > 1, {F: stride H W C}
+ *                (dspfft_plan_guru_r2r: REDFT10; the inverse REDFT01 with dspfft_plan_guru_r2r_ordered(..., 1), so that its column pass
+ *                begins it), with motion's scales.
+ *   d_work       F H W C floats, sharing the layout element for element.  d_in == d_out is allowed.
+ *   filter       NULL: none, and only packed->components is read.  Otherwise active = (1, H, W), minbuf_hw = (H, W) and block_depth = 1 are the
+ *                call's own (those fields are checked, then not read); the band, the thresholds, preserve_dc and the quantiser are the
+ *                caller's, and packed->damp, boost and grey_add, by byte position, replace the filter's fields of those names exactly as above.
+ * The sequence is dspfft_execute_roundtrip_u8's on that pair: the forward row pass into d_work -- with the interleaved 8-bit row load where
+ * the pass has one and every line of bytes starts at a multiple of 4, after dspfft_u8_to_f32 otherwise --; the forward column pass, the filter
+ * and the inverse column pass as ONE kernel where both passes have the same listed column kernel, that kernel has the twin with the filter of
+ * packed pixels (spec_inst_rt_packed_a/b.hip; kernels compiled at plan time have none) and d_work is 16-byte aligned, else as forward column
+ * pass, dspfft_motion_filter_packed (below), inverse column pass; the inverse row pass with the interleaved 8-bit store where it has one, else
+ * dspfft_f32_to_u8(out_mul).  No filter, or one in which nothing but the quantiser acts on any component, runs in the planar fused kernel: the
+ * bytes are the same.  DSPFFT_NO_FUSED_ROUNDTRIP=1 selects the unfused column sequence.  The bytes and the coded count EQUAL those of the
+ * composition dspfft_u8_to_f32 -> dspfft_execute(fwd) -> dspfft_motion_filter_packed -> dspfft_execute(inv) -> dspfft_f32_to_u8(out_mul).
+ * dspfft_plan_set_u8_trc on either plan (motion --linear) is honoured by the flat sweep dspfft_u8_to_f32_trc / dspfft_f32_to_u8_trc at that
+ * end, which then does not ride on the row pass.  A filtered call whose work buffer holds 2^31 elements or more runs the UNFUSED column
+ * sequence: the fused kernel addresses the clip with 31-bit offsets, the stand-alone kernel's are frame-local.
+ * Stream-ordered, allocates nothing.  Nothing is launched when it fails, the reason in dspfft_last_error:
+ *   -1  a NULL plan, buffer, d_work or `packed`; an f64 plan; bad filter parameters
+ *   -2  components outside 2..4, or not the count of the plans' unit-stride batch level; a small-block pair (that is
+ *       dspfft_execute_roundtrip_u8_packed); rank 3 (one 3-D block, -b 0x0x0); different extents in fwd and inv (-s); a pair that is not the
+ *       dense in-place layout above with REDFT10 in fwd, REDFT01 in inv and inv running its column pass first; a frame of 2^32 samples or more
+ *   -3  a library built without the HIP kernels
+ * Not implemented on packed full frames, each refused where a call could ask for it: -d (the dither kernels have no pixel step),
+ * --coeff-limit (a component's frame is no contiguous run: this entry takes no limit), -s, one 3-D block, float and padded (rgb0) formats. */
+int dspfft_execute_roundtrip_u8_packed_frames(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
+                                              const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                              unsigned long long *d_coeffs_coded, void *hip_stream);
+
 /* motion --spectrogram and --ispectrogram (motion/motion.c:617-776 with `spec` / `ispec` set) as one call per clip: the two halves of
  * the roundtrip above, each with ONE plan.
  *   spectrogram   load (:621-625) -> REDFT10 over `fwd`'s extents (`fwd` carries motion's index-0 factors, dspfft_plan_set_axis_scale0,
@@ -746,6 +780,18 @@ int dspfft_motion_spec_blocks_u8_packed(uint8_t *d_pix, const float *d_coeffs, i
                                         const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *hip_stream);
 int dspfft_motion_ispec_blocks_u8_packed(float *d_coeffs, const uint8_t *d_pix, int h, int w, int components, size_t frames, const dspfft_motion_spec_params *sp,
                                          const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *hip_stream);
+/* motion's coefficient filter (motion.c:683-744; dspfft_motion_filter below is the planar form) over `frames` dense frames [h][w][components]
+ * of coefficients in d_coeffs, in place: the middle step of dspfft_execute_roundtrip_u8_packed_frames where its column passes run unfused
+ * (motion_filter_packed.hip).  Every component of a frame is a block of its own: element e of a frame lies in row e / (w components), at pixel
+ * x = (e mod (w components)) / components, in component e mod components, and goes through the filter at (0, y, x) with that component's
+ * packed->damp, boost and grey_add (by byte position; the filter's fields of those names are not read).  filter->active = (d, h', w') in
+ * pixels: pixels outside it stay as they are; minbuf_hw and block_depth are checked, not read.  A thread moves a float4 where w * components is
+ * a multiple of 4 and d_coeffs 16-byte aligned, one coefficient otherwise; frames go along the grid's y, so offsets stay frame-local (a frame
+ * of 2^32 samples or more is refused); d_coeffs_coded takes one atomic per wave.  The coefficients EQUAL those of dspfft_motion_filter on each
+ * de-interleaved component with that component's damp, boost and grey_add, the count their sum.  components must be 2, 3 or 4 and equal
+ * packed->components.  Errors: dspfft_motion_last_error. */
+int dspfft_motion_filter_packed(float *d_coeffs, int h, int w, int components, size_t frames, const dspfft_motion_filter_params *filter,
+                                const dspfft_motion_packed *packed, unsigned long long *d_coeffs_coded, void *hip_stream);
 /* the float-pixel pair with motion --linear, which the reference applies with --ispec / --spec none (and copy on the store) only:
  * load  pel = sample * 255 (a float product); coeff = (float)(decode(pel / 255) * 255)          (motion.c:623,633)
  * store pel = coeff * scalefactor * normalization; pel *= normalization; sample = (float)(encode(pel / 255) * 255 / 255)   (:759,767-769,774)
