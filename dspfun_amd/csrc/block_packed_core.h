@@ -69,15 +69,18 @@ DSP_HD float packed_pick(const float (&v)[PACKED_MAX_COMPS], int c)
 	for (int k = 1; k < C; k++) r = c == k ? v[k] : r;
 	return r;
 }
-// the call's filter as component c sees it; quant_only depends on damp and boost (motion_filter_set_divs) and goes with them
-template <int C>
-DSP_HD MotionFilter packed_filter_of(const BlockPackedArgs &a, int c)
+// the call's filter as component c sees it; quant_only depends on damp and boost (motion_filter_set_divs) and goes with them.  Args: whatever
+// holds the three per-byte arrays; shared: every other field (block_rs_packed_core.h keeps them in its tile's scalars)
+template <int C, class Args>
+DSP_HD MotionFilter packed_filter_of(const Args &a, int c, const MotionFilter &shared)
 {
-	MotionFilter f = a.filt;
+	MotionFilter f = shared;
 	f.damp = packed_pick<C>(a.damp, c); f.boost = packed_pick<C>(a.boost, c); f.grey_add = packed_pick<C>(a.grey_add, c);
 	f.quant_only = f.quantizer > 0.f && f.damp == 1.f && f.boost == 1.f && !(f.thr_hi > 0.f) && (f.preserve_dc == 0 || !(f.b0d || f.b0h || f.b0w));
 	return f;
 }
+template <int C>
+DSP_HD MotionFilter packed_filter_of(const BlockPackedArgs &a, int c) { return packed_filter_of<C>(a, c, a.filt); }
 
 // component c of the NX pixels held in w: the bytes as floats, or (TRC) through the decode table
 template <int NX, int C, bool TRC>

@@ -31,6 +31,7 @@
 #include "block_rt.h"
 #include "block_rs_core.h"
 #include "block_packed_core.h"
+#include "block_rs_packed_core.h"
 #include "temporal_core.h"
 #include "block_spec_core.h"
 #include "block_spec_packed_core.h"
@@ -73,6 +74,7 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_
 // block_rescale_topn.hip's launcher behind the same with a coefficient limit (dspfft_execute_roundtrip_limit and its kin).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_topn_launch(const dspfft::BlockRsTopnArgs *a, int nwg, size_t lds, void *stream);
 // block_packed.hip's launcher behind dspfft_execute_roundtrip_u8_packed (packed 8-bit pixels through the fused block roundtrip).  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_packed_launch(const dspfft::BlockRsPackedArgs *a, int nwg, size_t lds, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_packed_launch(const dspfft::BlockPackedArgs *a, int nwg, size_t lds, void *stream);
 // temporal_rt.hip's launcher behind a roundtrip over blocks along time (motion -b 1x1xD).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_temporal_rt_launch(const dspfft::TemporalArgs *a, int nwg, void *stream);
@@ -1837,6 +1839,7 @@ struct RtArgs {
 	Dither dither;                        // out8 non-NULL (d_out8 NULL): the inverse ends in d_out as floats and the dither kernel stores the bytes from there
 	const dspfft_motion_packed *packed;   // non-NULL: dspfft_execute_roundtrip_u8_packed's call, d_in8 / d_out8 hold packed->components bytes per pixel
 	bool packed_frames;                   // ... dspfft_execute_roundtrip_u8_packed_frames's: the interleaved full-frame pair, d_out is the float work buffer
+	bool packed_rescale;                  // ... dspfft_execute_roundtrip_u8_packed_rescale's: a rescaled block grid, out of place
 	bool may_slice = true;               // false: a slice of a clip (roundtrip_sliced)
 };
 // ... and what rt_check derives from them for the runners (zero before)
@@ -1856,6 +1859,7 @@ struct RtCall : RtArgs {
 	bool temporal;                        // blocks along time that the plans' own passes cannot run (rt_temporal): temporal_rt.hip's kernel runs the call
 	TemporalArgs tp;                      // its arguments but the tables (rt_run_temporal)
 	BlockPackedArgs pk;                   // packed pixels (rt_packed): block_packed.hip's kernel runs the call
+	BlockRsPackedArgs pg;                 // packed pixels over a rescaled block grid (rt_packed_grid): block_rescale_packed.hip's kernel runs the call
 	MotionFilterPacked mfp;               // packed pixels over full frames (rt_packed_frames): the filter of the fused column kernel's twin,
 	dspfft_motion_filter_params pf_fp;    // ... and of the stand-alone kernel (the call's, with the frame's geometry), over
 	int pf_h, pf_w; long long pf_frames;  // ... that many frames of h x w pixels
@@ -1918,6 +1922,22 @@ void rt_block_args(const RtCall &c, BlockRtArgs &a)
 	a.filt = c.mf; a.coded = c.coded;
 }
 
+constexpr const char *kGrid = "roundtrip with different forward / inverse extents over a grid of blocks";
+constexpr const char *kGridBlocks = "every extent of both plans must be 4, 8 or 16 (2-D blocks: 32 too), x contiguous, all strides multiples of 4 (a single block goes with howmany = 1)";
+// what a grid asks of its pair beyond different extents (rt_grid, rt_packed_grid); no_blocks: the reason given for a plan without small blocks
+int rt_grid_pair(const dspfft_plan_s *fwd, const dspfft_plan_s *inv, const char *what, const char *no_blocks)
+{
+	if (fwd->rank != inv->rank) return fail(-2, "%s: the plans have different ranks (%d-D blocks against %d-D blocks)", what, fwd->rank, inv->rank);
+	if (!fwd->has_block || !inv->has_block) return fail(-2, "%s: %s", what, no_blocks);
+	if (fwd->blk_kind != KIND_REDFT10 || inv->blk_kind != KIND_REDFT01) return fail(-2, "%s: the forward plan must be REDFT10 and the inverse REDFT01 on every axis", what);
+	const BlockGeom &f = fwd->blk, &i = inv->blk;
+	for (int k = 0; k < 3; k++) if (fwd->blk_axis[k] != inv->blk_axis[k]) return fail(-2, "%s: the plans order their axes differently", what);
+	if (f.rows_fast != i.rows_fast) return fail(-2, "%s: one plan is a block-major stack and the other the blocks of a volume", what);
+	bool same = f.nxb == i.nxb && f.nd == i.nd;
+	for (int d = 0; same && d < f.nd; d++) same = f.bn[d] == i.bn[d];
+	if (!same || fwd->howmany != inv->howmany) return fail(-2, "%s: the plans count different numbers of blocks", what);
+	return 0;
+}
 // motion -b with -s over a block grid (motion.c:488-499,535-552): both plans cut their volumes into small blocks, `fwd` the input volume
 // into blocks of `block`, `inv` the output volume into as many blocks of `scaled`.  0: the pair is none (the call goes on as before: every
 // such pair was refused until now); 1: it is one, c.grid and c.rs are set and everything about the call is checked; < 0: it is almost one,
@@ -1926,17 +1946,9 @@ int rt_grid(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
 	if (!extents_differ(fwd, inv) || fwd->howmany < 2 || inv->howmany < 2) return 0;
-	const char *const what = "roundtrip with different forward / inverse extents over a grid of blocks";
-	if (fwd->rank != inv->rank) return fail(-2, "%s: the plans have different ranks (%d-D blocks against %d-D blocks)", what, fwd->rank, inv->rank);
-	if (!fwd->has_block || !inv->has_block)
-		return fail(-2, "%s: every extent of both plans must be 4, 8 or 16 (2-D blocks: 32 too), x contiguous, all strides multiples of 4 (a single block goes with howmany = 1)", what);
-	if (fwd->blk_kind != KIND_REDFT10 || inv->blk_kind != KIND_REDFT01) return fail(-2, "%s: the forward plan must be REDFT10 and the inverse REDFT01 on every axis", what);
+	const char *const what = kGrid;
+	if (int rc = rt_grid_pair(fwd, inv, what, kGridBlocks)) return rc;
 	const BlockGeom &f = fwd->blk, &i = inv->blk;
-	for (int k = 0; k < 3; k++) if (fwd->blk_axis[k] != inv->blk_axis[k]) return fail(-2, "%s: the plans order their axes differently", what);
-	if (f.rows_fast != i.rows_fast) return fail(-2, "%s: one plan is a block-major stack and the other the blocks of a volume", what);
-	bool same = f.nxb == i.nxb && f.nd == i.nd;
-	for (int d = 0; same && d < f.nd; d++) same = f.bn[d] == i.bn[d];
-	if (!same || fwd->howmany != inv->howmany) return fail(-2, "%s: the plans count different numbers of blocks", what);
 	if (!dspfft_block_rescale_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale.hip)", what);
 	const int mx = std::max(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
 	unsigned int limit = 0;
@@ -2172,6 +2184,67 @@ int rt_run_packed(const RtCall &c)
 	return 0;
 }
 
+// ---- motion -b with -s on packed 8-bit pixels (include/dspfft.h): rt_grid's pair -- the PLANAR grid pair over the clip in pixels -- with every stride
+// and offset times `components`, block_rescale_packed.hip's kernel.  The entry has refused null plans, buffers and c.packed and f64 plans.
+// 0: c.pg is set; < 0: the call cannot run.  Nothing is launched here.
+constexpr const char *kPackedGrid = "roundtrip on packed 8-bit pixels over a rescaled grid of blocks";
+// the pixels from a clip's first to one past its last, as the plan's block geometry lays it out (out: the output side)
+long long block_clip_span(const BlockGeom &g, bool out)
+{
+	long long span = (long long)(g.nxb - 1) * (out ? g.sxb_out : g.sxb_in) + (long long)(g.nz - 1) * (out ? g.sz_out : g.sz_in) + (long long)(g.ny - 1) * (out ? g.sy_out : g.sy_in) + g.nx;
+	for (int d = 0; d < g.nd; d++) span += (long long)(g.bn[d] - 1) * (out ? g.bos[d] : g.bis[d]);
+	return span;
+}
+int rt_packed_grid(RtCall &c)
+{
+	const dspfft_plan fwd = c.fwd, inv = c.inv;
+	const char *const what = kPackedGrid;
+	if (int rc = rt_filter(c, what)) return rc;
+	const int C = c.packed->components;
+	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
+	if (!extents_differ(fwd, inv)) return fail(-2, "%s: the plans have equal extents: that pair is dspfft_execute_roundtrip_u8_packed's (small blocks) or dspfft_execute_roundtrip_u8_packed_frames's", what);
+	if (fwd->howmany < 2 || inv->howmany < 2) return fail(-2, "%s: one block with different extents (howmany = 1) is not implemented on packed pixels", what);
+	if (int rc = rt_grid_pair(fwd, inv, what, "every extent of both plans must be 4, 8 or 16 (2-D blocks: 32 too), x contiguous, all strides multiples of 4; full frames of packed pixels are "
+	                          "dspfft_execute_roundtrip_u8_packed_frames's, which takes equal extents only (motion -s over full frames is not implemented)")) return rc;
+	if (!rt_ends_aligned(c)) return fail(-2, "%s: the buffers must be 4-byte aligned", what);
+	const BlockGeom &f = fwd->blk, &i = inv->blk;
+	// out of place by nature: the two clips, in bytes
+	const uintptr_t in0 = (uintptr_t)c.d_in8, out0 = (uintptr_t)c.d_out8;
+	const unsigned long long in_bytes = (unsigned long long)block_clip_span(f, false) * C, out_bytes = (unsigned long long)block_clip_span(i, true) * C;
+	if (in0 < out0 + out_bytes && out0 < in0 + in_bytes)
+		return fail(-2, "%s: the input clip (%llu bytes) and the output clip (%llu bytes) overlap; the call is out of place (the clips have different extents)", what, in_bytes, out_bytes);
+	rt_trc_ends(c);
+	BlockRsPackedArgs &a = c.pg;
+	memset((void *)&a, 0, sizeof a);
+	rt_block_args(c, a);
+	rt_tables(c, a);
+	a.ox = i.nx; a.oy = i.ny; a.oz = i.nz;
+	// the plans count pixels; the kernel addresses bytes
+	a.sy_in *= C; a.sz_in *= C; a.sxb_in *= C; a.sy_out *= C; a.sz_out *= C; a.sxb_out *= C;
+	long long nwg = 1;
+	for (int d = 0; d < a.nd; d++) { a.bis[d] *= C; a.bos[d] *= C; nwg *= a.bn[d]; }
+	// the tile of a component block: the embedding's rows and planes, the active columns (block_rs_packed_core.h)
+	const int mx = std::min(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
+	int G = rs_packed_group_of(mx, my, mz, f.ny * f.nz, i.ny * i.nz, C, a.nxb);
+	if (const char *e = getenv("DSPFFT_PACKED_G")) { if (atoi(e) > 0) G = std::min(atoi(e), a.nxb); }      // experiments (tools/bench_motion_packed_rescale.py)
+	const size_t block_bytes = (size_t)mz * my * C * mx * sizeof(float);
+	G = rt_lds_group(G, block_bytes);
+	if (!G) return fail(-2, "%s: the %d component tiles of a %dx%dx%d embedding (%zu bytes) and the tables do not fit a workgroup's 64 KB of LDS", what, C, std::max(f.nx, i.nx), my, mz, block_bytes);
+	a.tw = mx; a.G = G; a.pitch = G * C * mx; a.ngroups = (a.nxb + G - 1) / G; a.gdiv = make_div((uint32_t)a.ngroups);
+	nwg *= a.ngroups;
+	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch (more than 2^31 - 1 workgroups)", what);
+	a.comps = C;
+	if (c.fp) for (int k = 0; k < C; k++) { a.damp[k] = c.packed->damp[k]; a.boost[k] = c.packed->boost[k]; a.grey_add[k] = c.packed->grey_add[k]; }
+	if (!dspfft_block_rescale_packed_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale_packed.hip)", what);
+	c.nwg = (int)nwg; c.lds = (size_t)G * block_bytes;
+	return 0;
+}
+int rt_run_packed_grid(const RtCall &c)
+{
+	if (int rc = dspfft_block_rescale_packed_launch(&c.pg, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (%s): backend code %d", kPackedGrid, rc);
+	return 0;
+}
+
 // ---- motion on packed 8-bit pixels over full frames (the reference's default -b 0x0x1; include/dspfft.h): the interleaved rank-2 pair over
 // [F][h][w][C], run by rt_run_passes with the filter of packed pixels in the middle.  The entry has refused null plans, buffers, d_work and
 // c.packed and f64 plans.  0: the call is ready for rt_run_passes; < 0: it cannot run.  Nothing is launched here.
@@ -2229,7 +2302,7 @@ int rt_check(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
 	const dspfft_motion_filter_params *fp = c.fp;
-	if (c.packed) return c.packed_frames ? rt_packed_frames(c) : rt_packed(c);      // (their entries take no other strategy, and have seen to plans and buffers)
+	if (c.packed) return c.packed_frames ? rt_packed_frames(c) : c.packed_rescale ? rt_packed_grid(c) : rt_packed(c);      // (their entries take no other strategy, and have seen to plans and buffers)
 	if (!fwd || !inv || !(c.d_in || c.d_in8) || !(c.d_out || c.d_out8)) return fail(-1, "null plan or buffer");
 	if (fwd->f64 || inv->f64) return fail(-1, "the fused roundtrip takes f32 plans");
 	if (int t = rt_temporal(c)) return t < 0 ? t : 0;          // (ahead of rt_grid, which answers every rescaled pair with batches that it is no grid)
@@ -2573,7 +2646,7 @@ int roundtrip_core(RtCall &c)
 {
 	if (int rc = rt_check(c)) return rc;
 	int rc = 0;
-	if (c.packed) rc = c.packed_frames ? rt_run_passes(c) : rt_run_packed(c);
+	if (c.packed) rc = c.packed_frames ? rt_run_passes(c) : c.packed_rescale ? rt_run_packed_grid(c) : rt_run_packed(c);
 	else if (c.grid) rc = rt_run_grid(c);
 	else if (c.temporal) rc = rt_run_temporal(c);
 	else if (c.block) rc = rt_run_block(c);
@@ -3068,6 +3141,20 @@ extern "C" int dspfft_execute_roundtrip_u8_packed_frames(dspfft_plan fwd, dspfft
 	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", kPackedFrames);
 	RtCall c = {};
 	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.d_out = d_work; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.packed_frames = true;
+	c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
+}
+
+// ... over a rescaled block grid (rt_packed_grid): out of place, no work buffer, no coefficient limit
+extern "C" int dspfft_execute_roundtrip_u8_packed_rescale(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
+                                                          const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed,
+                                                          unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", kPackedGrid);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", kPackedGrid);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", kPackedGrid);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.packed_rescale = true;
 	c.coded = d_coeffs_coded; c.stream = stream;
 	return roundtrip_core(c);
 }

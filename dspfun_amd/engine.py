@@ -263,6 +263,17 @@ class Plan:
         self._check(self._lib.dspfft_execute_roundtrip_u8_packed(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
                                                                  *self._tail(filter, d_coded, stream, *between)))
 
+    def roundtrip_u8_packed_rescale(self, inv, d_in_u8, d_out_u8, out_mul, packed, filter=None, d_coded=0, stream=0):
+        """dspfft_execute_roundtrip_u8_packed_rescale: motion -b with -s over a block grid on packed 8-bit pixels (rgb24, rgba ...), one launch.
+        self / inv: the planar grid pair motion_grid_plans(shape, block, scaled) with scaled != block, planned over the clips in pixels; d_in_u8
+        holds info["in_shape"] and d_out_u8 info["out_shape"] pixels of packed.components bytes, and the two must not overlap.  out_mul:
+        info["out_mul"].  packed: motion_packed(..., normalization=info["normalization"], scalefactor=info["scalefactor"]) -- its damp, boost
+        and grey_add (by byte position) replace the filter's; filter: the planar grid call's (active = info["active"], minbuf_hw and block_depth
+        of the embedding), or None.  Needs no work buffer and takes no coefficient limit."""
+        pk = C.byref(packed) if packed is not None else None
+        self._check(self._lib.dspfft_execute_roundtrip_u8_packed_rescale(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
+                                                                         *self._tail(filter, d_coded, stream, pk)))
+
     def roundtrip_u8_packed_frames(self, inv, d_in_u8, d_out_u8, d_work, out_mul, packed, filter=None, d_coded=0, stream=0):
         """dspfft_execute_roundtrip_u8_packed_frames: motion's default block 0x0x1 on packed 8-bit pixels (rgb24, rgba ...) -- every component of
         every frame one block.  self / inv: motion_packed_frame_plans(frames, h, w, components); d_work: frames * h * w * components floats;
@@ -417,6 +428,8 @@ def motion_packed(pix_fmt, boost=None, damp=None, dcstop=False, normalization=1.
     up to four values in the reference's component order (r:g:b:a), filled up by its rule (motion/motion.c:235-236: a missing entry repeats the
     one before it; none at all gives 1 for boost and 0 for damp).  grey_add[i] = (1 - (damp[i] if dcstop else boost[i])) 127.5 /
     (normalization^2 scalefactor) (:736; dcstop: the pass band does not begin at the origin).  All three are stored by BYTE POSITION.
+    With a rescaled pair (Plan.roundtrip_u8_packed_rescale) normalization and scalefactor are motion_grid_plans' info["normalization"] and
+    info["scalefactor"] (the latter is then not 1, :566), and the line gives the pair's grey_add as it stands.
     Formats with a byte that is no component (rgb0, 0rgb ...: the reference never writes it), gray (the planar call) and anything that is not
     8-bit are refused with a ValueError."""
     fmt = str(pix_fmt)

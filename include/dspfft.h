@@ -420,8 +420,8 @@ int dspfft_execute_roundtrip_u8_dither_limit(dspfft_plan fwd, dspfft_plan inv, c
  * uses no work buffer.  Nothing is launched when it fails:
  *   -1  a NULL plan, buffer or `packed`; an f64 plan; cl with keep == 0; bad filter parameters
  *   -2  components outside 2..4; a pair the fused block pass does not take (per-frame plans, one 3-D block); different extents in fwd and
- *       inv (a rescaled grid: motion -s is not implemented on packed pixels, nor are -d and --spectrogram / --ispectrogram); buffers off
- *       4 bytes; a block whose `components` tiles plus the tables do not fit one workgroup's 64 KB of LDS -- of the listed extents that is
+ *       inv (a rescaled grid, motion -s: that pair is dspfft_execute_roundtrip_u8_packed_rescale's, below; -d and --spectrogram /
+ *       --ispectrogram are not implemented on packed small blocks); buffers off 4 bytes; a block whose `components` tiles plus the tables do not fit one workgroup's 64 KB of LDS -- of the listed extents that is
  *       16 x 16 x 16 at four components --; more than 2^31 - 1 workgroups
  *   -3  a library built without the HIP kernel */
 typedef struct {
@@ -433,7 +433,39 @@ int dspfft_execute_roundtrip_u8_packed(dspfft_plan fwd, dspfft_plan inv, const u
                                        const dspfft_coeff_limit *cl /* NULL: no --coeff-limit */,
                                        unsigned long long *d_coeffs_coded, void *hip_stream);
 
-/* The same on FULL FRAMES of packed pixels -- the reference's default block -b 0x0x1, what `motion -q 20 in.png out.png` or
+/* The same with `scaled != block` over a grid of blocks (motion -b 8x8x8 -s 4x4x4 -c pixel_format=rgb24: motion/motion.c:488-499,535-552
+ * with the components of :155-156,613-615): every component of every pixel block is transformed over `block` (REDFT10), filtered over
+ * A = min(block, scaled) and transformed back over `scaled` (REDFT01) inside the embedding M = max(block, scaled) (:617), and the output
+ * clip has other extents than the input clip.  ONE kernel (block_rescale_packed.hip: the rescaled grid's pruned phases between the packed
+ * ends), so the call moves components * (input pixels + output pixels) bytes, where splitting the clip into planes, one planar grid call per
+ * plane and interleaving again moves about three times that.  An entry of its own because the call is out of place by nature.
+ *   fwd, inv     the PLANAR grid pair of dspfft_execute_roundtrip_u8 on a rescaled block grid (above: `fwd` cuts the input clip into blocks
+ *                of `block`, `inv` the output clip into as many blocks of `scaled`; volume layout or block-major stacks; every extent 4, 8 or
+ *                16, 2-D blocks up to 32), planned over the clips in PIXELS; the call multiplies every stride and offset by `components`.  The
+ *                bytes of this call EQUAL those of the planar grid call on each component's plane with that component's damp, boost and
+ *                grey_add, and d_coeffs_coded the sum of the planar counts.
+ *   filter       the planar grid's: active = min(block, scaled), minbuf_hw and block_depth describe the embedding.  packed->damp, boost and
+ *                grey_add, by BYTE POSITION, replace the filter's fields of those names, which are not read.  NULL: none, and only
+ *                packed->components is read.
+ *   dspfft_plan_set_u8_trc on either plan is honoured at that end, as in the planar call.
+ * Stream-ordered, allocates nothing, uses no work buffer.  Nothing is launched when it fails, the reason in dspfft_last_error:
+ *   -1  a NULL plan, buffer or `packed`; an f64 plan; bad filter parameters
+ *   -2  components outside 2..4; a pair with equal extents (dspfft_execute_roundtrip_u8_packed, or _packed_frames); one block (howmany = 1)
+ *       or a per-frame pair (full frames are dspfft_execute_roundtrip_u8_packed_frames's, with equal extents only); what the planar grid
+ *       refuses of a pair: different ranks, an extent that is not 4, 8 or 16 (2-D: 32), kinds, axis orders, a stack against a volume,
+ *       different numbers of blocks; buffers off 4 bytes; an input clip and an output clip whose byte ranges intersect (d_in == d_out is the
+ *       simplest case); a pair whose `components` tiles (the embedding's planes and rows by min(block, scaled) columns) plus the tables do not
+ *       fit one workgroup's 64 KB of LDS -- a 16 x 16 x 16 embedding with 16 columns on both sides at four components --; more than
+ *       2^31 - 1 workgroups
+ *   -3  a library built without the HIP kernel
+ *   -4  a launch failure
+ * Not implemented on a packed rescaled grid, each refused where a call could ask for it: --coeff-limit (this entry takes no limit), -d,
+ * --spectrogram / --ispectrogram, -s over full frames or one block, float and padded (rgb0) formats. */
+int dspfft_execute_roundtrip_u8_packed_rescale(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
+                                               const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                               unsigned long long *d_coeffs_coded, void *hip_stream);
+
+/* The small-block call on FULL FRAMES of packed pixels -- the reference's default block -b 0x0x1, what `motion -q 20 in.png out.png` or
  * `motion -c pixel_format=rgb24` on a clip runs: every component of every frame is one block (:613-615).  An entry of its own because the
  * passes of full frames need a float work buffer, which the small-block entry has no argument for.
  *   fwd, inv     the caller's in-place, dense, interleaved f32 pair of rank 2 over [F][H][W][C], the plans of the full-frame spectrogram calls
