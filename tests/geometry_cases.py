@@ -94,7 +94,7 @@ class Case:
     def reference(self, x):
         """dense float64 [batch..., axes...] result for the input buffer x"""
         nb, rank = len(self.how), len(self.dims)
-        dense = np.ascontiguousarray(self.view(x, 1), dtype=np.float64)
+        dense = np.array(self.view(x, 1), dtype=np.float64)     # a copy, also of a dense f64 input: the input scale below must not reach x
         n = [d[0] for d in self.dims]
         if self.scaled_axis is not None:
             sl = [slice(None)] * dense.ndim
