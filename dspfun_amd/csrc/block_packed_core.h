@@ -19,6 +19,7 @@
 // Plain C++17 for device (hipcc) and the CPU emulation of the phases (g++, tests/test_motion_packed_cpu.py).
 #pragma once
 #include "block_core.h"
+#include "dither_core.h"
 #include "topn_core.h"
 
 namespace dspfft {
@@ -205,6 +206,89 @@ DSP_HD void packed_filter_sweep(const BlockPackedArgs &a, float *lds, int cnt, i
 			float *p = lds + row * a.pitch + c;
 			*p = motion_filter_at(f, bz, by, bx, *p, coded);
 		}
+	}
+}
+
+// ---- motion -d on packed small blocks (dspfft_execute_roundtrip_u8_packed_dither, block_packed_dither.hip): the store of the sequences above in
+// three phases, a barrier after each of the first two.  When the y phase of the inverse ends, every z plane of every tile block is an NY x NX plane
+// of the Floyd-Steinberg store (motion.c:778-787 walks each plane of each component block on its own) and lies in LDS whole.
+//   inverse x   thread = one x line of a pixel block, as in packed_store_x, but the transformed line goes back to its slot of the tile: the
+//               floats the planar kernel would store to the dithered call's work buffer
+//   dither      thread = one plane, raster order (dither_plane_tile); the byte takes the float's slot.  The previous row's errors lie in LDS
+//               lane-major (no dynamically indexed registers); the planes are dealt to the four waves in equal shares, because a plane is a
+//               dependent chain of NY NX steps in double and a wave takes as long over one lane as over 64
+//   store       packed_store_x's addresses and dwords, the bytes taken from the tile
+struct BlockPackedDitherArgs : BlockPackedArgs {   // out8: the dithered bytes; mul8 is not read
+	double sf, norm;                               // motion's scalefactor and normalization (dither_core.h)
+	int slots;                                     // dither lanes of a full tile (packed_dither_slots): each has NX doubles of LDS behind the error table
+};
+// lanes per wave that take a plane when the tile holds `nplanes`
+DSP_HD int packed_dither_lanes(int nplanes)
+{
+	const int q = (nplanes + BLOCK_THREADS / 64 - 1) / (BLOCK_THREADS / 64);
+	return q > 64 ? 64 : q;
+}
+DSP_HD int packed_dither_slots(int nz, int comps, int G) { return (BLOCK_THREADS / 64) * packed_dither_lanes(nz * comps * G); }
+// LDS of the dither phase behind the tile and the transfer tables: the 256 doubles of dither_table, then the lanes' error rows
+DSP_HD size_t packed_dither_bytes(int nx, int slots) { return (256 + (size_t)slots * nx) * sizeof(double); }
+
+template <int NX, int NY, int NZ, int C>
+DSP_HD void packed_inverse_x(const BlockGeom &a, const TinyArgs &tx, float *lds, int cnt, int tid)
+{
+	const int lines = NZ * NY * cnt;
+	for (int l = tid; l < lines; l += BLOCK_THREADS) {
+		int row, g;
+		block_line_of(a, l, NZ * NY, cnt, row, g);
+#pragma unroll
+		for (int c = 0; c < C; c++) {
+			float x[NX], o[NX];
+			float4 *q = reinterpret_cast<float4 *>(lds + row * a.pitch + (c * cnt + g) * NX);
+#pragma unroll
+			for (int j = 0; j < NX / 4; j++) { const float4 v = q[j]; x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w; }
+			tiny_dct<NX, KIND_REDFT01>(tx, x, o);
+#pragma unroll
+			for (int j = 0; j < NX / 4; j++) { float4 v; v.x = o[4 * j]; v.y = o[4 * j + 1]; v.z = o[4 * j + 2]; v.w = o[4 * j + 3]; q[j] = v; }
+		}
+	}
+}
+// tab: dither_table(sf, norm); dprow: a.slots * NX doubles; thr NULL: the plain byte, else the threshold table of the inverse plan's characteristic
+template <int NX, int NY, int NZ, int C>
+DSP_HD void packed_dither_tile(const BlockPackedDitherArgs &a, float *lds, int cnt, int tid, const double *tab, double *dprow, const double *thr, const TrcParams &tp)
+{
+	const int nb = cnt * C, nplanes = NZ * nb, q = packed_dither_lanes(nplanes), wave = tid >> 6, lane = tid & 63;
+	if (lane >= q) return;
+	const int slot = wave * q + lane, nslots = (BLOCK_THREADS / 64) * q;
+	for (int pl = slot; pl < nplanes; pl += nslots) {
+		const int z = pl / nb, gb = pl - z * nb;
+		float *plane = lds + z * NY * a.pitch + gb * NX;
+		if (thr) dither_plane_tile<true>(plane, a.pitch, NY, NX, a.sf, a.norm, tab, dprow + slot, nslots, thr, &tp);
+		else dither_plane_tile<false>(plane, a.pitch, NY, NX, a.sf, a.norm, tab, dprow + slot, nslots);
+	}
+}
+template <int NX, int NY, int NZ, int C>
+DSP_HD void packed_store_bytes(const BlockGeom &a, uint8_t *out8, const float *lds, long long bout, int cnt, int tid)
+{
+	constexpr int W = NX * C / 4;
+	const int lines = NZ * NY * cnt;
+	for (int l = tid; l < lines; l += BLOCK_THREADS) {
+		int row, g;
+		block_line_of(a, l, NZ * NY, cnt, row, g);
+		const int z = row / NY, y = row - z * NY;
+		const long long off = bout + (long long)g * a.sxb_out + (long long)z * a.sz_out + (long long)y * a.sy_out;
+		uint32_t w[W];
+#pragma unroll
+		for (int j = 0; j < W; j++) w[j] = 0;
+#pragma unroll
+		for (int c = 0; c < C; c++) {
+			const float *q = lds + row * a.pitch + (c * cnt + g) * NX;
+#pragma unroll
+			for (int p = 0; p < NX; p++) {
+				const int i = C * p + c;
+				w[i >> 2] |= dither_tile_byte(q + p) << (8 * (i & 3));
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < W; j++) __builtin_memcpy(out8 + off + 4 * j, &w[j], 4);
 	}
 }
 

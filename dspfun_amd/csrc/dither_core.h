@@ -89,6 +89,54 @@ DSP_HD void dither_plane_serial(uint8_t *out, const float *in, long long pitch, 
 	}
 }
 
+// The raster walk once more, over a plane that is not a dense run of floats beside a dense run of bytes: get(y, x) is the pixel's float and
+// put(y, x, byte) takes its byte.  A pixel's float is read once, by that pixel and before its put, so put may overwrite what get reads.
+template <bool TRC = false, class Get, class Put>
+DSP_HD void dither_plane_raster(Get get, Put put, int h, int w, double scalefactor, double norm, const double *tab, double *dprow, int dstride,
+                                const double *thr = nullptr, const TrcParams *tp = nullptr)
+{
+	DITHER_NO_CONTRACT
+	for (int y = 0; y < h; y++) {
+		const bool up = y > 0;
+		double dm = 0, d0 = 0, dq = up ? dprow[0] : 0.0, dl = 0;
+		for (int x = 0; x < w; x++) {
+			dm = d0; d0 = dq;
+			const bool xp = x + 1 < w;
+			dq = (up && xp) ? dprow[(long long)(x + 1) * dstride] : 0.0;
+			double dp;
+			put(y, x, dither_pel<TRC>(get(y, x), up, x > 0, xp, dm, d0, dq, dl, scalefactor, norm, tab, dp, thr, tp));
+			if (x > 0) dprow[(long long)(x - 1) * dstride] = dl;
+			dl = dp;
+		}
+		dprow[(long long)(w - 1) * dstride] = dl;
+	}
+}
+// ... a component's plane of packed pixels: columns `step` elements apart in `in` and `out` alike (step 1 is dither_plane_serial)
+template <bool TRC = false>
+DSP_HD void dither_plane_step(uint8_t *out, const float *in, long long pitch, int step, int h, int w, double scalefactor, double norm, const double *tab,
+                              double *dprow, int dstride, const double *thr = nullptr, const TrcParams *tp = nullptr)
+{
+	DITHER_NO_CONTRACT
+	dither_plane_raster<TRC>([=](int y, int x) { return in[(long long)y * pitch + (long long)x * step]; },
+	                         [=](int y, int x, uint8_t b) { out[(long long)y * pitch + (long long)x * step] = b; }, h, w, scalefactor, norm, tab, dprow, dstride, thr, tp);
+}
+// ... a plane of a fused block kernel's LDS tile, in place: the float at (y, x) makes way for its byte, held as a 32-bit integer in the same slot
+// (dither_tile_byte reads it back)
+template <bool TRC = false>
+DSP_HD void dither_plane_tile(float *tile, int pitch, int h, int w, double scalefactor, double norm, const double *tab, double *dprow, int dstride,
+                              const double *thr = nullptr, const TrcParams *tp = nullptr)
+{
+	DITHER_NO_CONTRACT
+	dither_plane_raster<TRC>([=](int y, int x) { return tile[y * pitch + x]; },
+	                         [=](int y, int x, uint8_t b) { const uint32_t v = b; __builtin_memcpy(tile + y * pitch + x, &v, 4); }, h, w, scalefactor, norm, tab, dprow, dstride, thr, tp);
+}
+DSP_HD uint32_t dither_tile_byte(const float *slot)
+{
+	uint32_t v;
+	__builtin_memcpy(&v, slot, 4);
+	return v;
+}
+
 // The same plane in the device kernel's wavefront order: every pixel with the same x + 2y at once (a pixel depends on (y, x-1) and
 // (y-1, x-1 .. x+1), all on earlier anti-diagonals).  dp: h * w doubles of scratch.  Host-side check that the order does not change a byte.
 DSP_HD void dither_plane_wavefront(uint8_t *out, const float *in, long long pitch, int h, int w, double scalefactor, double norm, const double *tab,

@@ -76,6 +76,11 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_
 // block_packed.hip's launcher behind dspfft_execute_roundtrip_u8_packed (packed 8-bit pixels through the fused block roundtrip).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_packed_launch(const dspfft::BlockRsPackedArgs *a, int nwg, size_t lds, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_packed_launch(const dspfft::BlockPackedArgs *a, int nwg, size_t lds, void *stream);
+// block_packed_dither.hip's launcher behind dspfft_execute_roundtrip_u8_packed_dither, and motion_dither.hip's behind dspfft_motion_dither_u8_packed
+// (dry: its checks alone).  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_packed_dither_launch(const dspfft::BlockPackedDitherArgs *a, int nwg, size_t lds, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_dither_packed_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, int comps, double scalefactor,
+                                                                                       double normalization, int trc, const void *tab, int dry, void *stream, char *err, size_t errlen);
 // temporal_rt.hip's launcher behind a roundtrip over blocks along time (motion -b 1x1xD).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_temporal_rt_launch(const dspfft::TemporalArgs *a, int nwg, void *stream);
 // block_spec.hip's and motion_ops.hip's launchers behind dspfft_execute_spectrogram_* / _ispectrogram_*.  Weak, as above.
@@ -1836,7 +1841,8 @@ struct RtArgs {
 	const dspfft_motion_filter_params *fp; unsigned long long *coded; void *stream;
 	size_t keep; void *topn_work; size_t topn_work_bytes;       // motion --coeff-limit (rt_limit); keep = 0: none
 	double outside_mul;                   // > 0: the call came through a dspfft_execute_roundtrip*_limit entry, which takes a limit on a rescaled block grid
-	Dither dither;                        // out8 non-NULL (d_out8 NULL): the inverse ends in d_out as floats and the dither kernel stores the bytes from there
+	Dither dither;                        // out8 non-NULL (d_out8 NULL): the inverse ends in d_out as floats and the dither kernel stores the bytes from there;
+	                                      // out8 = d_out8 (packed small blocks): the call's one kernel dithers in its tile and stores the bytes itself
 	const dspfft_motion_packed *packed;   // non-NULL: dspfft_execute_roundtrip_u8_packed's call, d_in8 / d_out8 hold packed->components bytes per pixel
 	bool packed_frames;                   // ... dspfft_execute_roundtrip_u8_packed_frames's: the interleaved full-frame pair, d_out is the float work buffer
 	bool packed_rescale;                  // ... dspfft_execute_roundtrip_u8_packed_rescale's: a rescaled block grid, out of place
@@ -1858,7 +1864,7 @@ struct RtCall : RtArgs {
 	BlockRsTopnArgs rs;                   // its arguments, with the geometry derived for the pair (keep = 0: no coefficient limit; block_rescale_topn.hip's kernel otherwise)
 	bool temporal;                        // blocks along time that the plans' own passes cannot run (rt_temporal): temporal_rt.hip's kernel runs the call
 	TemporalArgs tp;                      // its arguments but the tables (rt_run_temporal)
-	BlockPackedArgs pk;                   // packed pixels (rt_packed): block_packed.hip's kernel runs the call
+	BlockPackedDitherArgs pk;             // packed pixels (rt_packed): block_packed.hip's kernel runs the call, or (c.dither) block_packed_dither.hip's
 	BlockRsPackedArgs pg;                 // packed pixels over a rescaled block grid (rt_packed_grid): block_rescale_packed.hip's kernel runs the call
 	MotionFilterPacked mfp;               // packed pixels over full frames (rt_packed_frames): the filter of the fused column kernel's twin,
 	dspfft_motion_filter_params pf_fp;    // ... and of the stand-alone kernel (the call's, with the frame's geometry), over
@@ -2142,19 +2148,23 @@ int packed_frames_layout(const dspfft_plan_s *pl, int C, const char *what, long 
 }
 
 constexpr const char *kPacked = "roundtrip on packed 8-bit pixels";
+constexpr const char *kPackedDither = "dithered roundtrip on packed 8-bit pixels";
 int rt_packed(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
-	const char *const what = kPacked;
+	const bool dither = c.dither.out8 != nullptr;           // motion -d: the store's three phases in the tile (block_packed_core.h)
+	const char *const what = dither ? kPackedDither : kPacked;
 	if (int rc = rt_filter(c, what)) return rc;
 	const int C = c.packed->components;
 	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
+	if (dither && extents_differ(fwd, inv) && fwd->has_block && inv->has_block)
+		return fail(-2, "%s: different forward / inverse extents: -d on a packed rescaled grid is not implemented (the tile keeps min(block, scaled) columns and has no room for the scaled planes)", what);
 	if (extents_differ(fwd, inv) && fwd->has_block && inv->has_block) return fail(-2, "%s: different forward / inverse extents (a rescaled block grid, motion -s) are not implemented on packed pixels", what);
 	if (!block_roundtrip_ok(fwd, inv))
 		return fail(-2, "%s needs the plan pair of the fused block pass: matching REDFT10 / REDFT01 small-block plans (every extent 4, 8 or 16, 2-D blocks up to 32; per-frame and single-block plans have no block pass)", what);
 	if (!rt_ends_aligned(c)) return fail(-2, "%s: the buffers must be 4-byte aligned", what);
 	rt_trc_ends(c);
-	BlockPackedArgs &a = c.pk;
+	BlockPackedDitherArgs &a = c.pk;
 	memset((void *)&a, 0, sizeof a);
 	rt_block_args(c, a);
 	rt_tables(c, a);
@@ -2166,6 +2176,10 @@ int rt_packed(RtCall &c)
 	if (const char *e = getenv("DSPFFT_PACKED_G")) { if (atoi(e) > 0) G = std::min(atoi(e), a.nxb); }      // experiments (tools/bench_motion_packed.py)
 	const size_t block_bytes = (size_t)a.nz * a.ny * C * a.nx * sizeof(float);
 	G = rt_lds_group(G, block_bytes);
+	// -d: the error table and the dither lanes' error rows lie behind the tile and the tables
+	while (dither && G > 0 && (size_t)G * block_bytes + sizeof(TrcU8Tab) + 16 + packed_dither_bytes(a.nx, packed_dither_slots(a.nz, C, G)) > 64 * 1024) G--;
+	if (!G && dither)
+		return fail(-2, "%s: the %d component tiles of a %dx%dx%d block (%zu bytes), the tables and the dither's error rows do not fit a workgroup's 64 KB of LDS", what, C, a.nx, a.ny, a.nz, block_bytes);
 	if (!G) return fail(-2, "%s: the %d component tiles of a %dx%dx%d block (%zu bytes) and the tables do not fit a workgroup's 64 KB of LDS", what, C, a.nx, a.ny, a.nz, block_bytes);
 	a.G = G; a.pitch = G * C * a.nx; a.ngroups = (a.nxb + G - 1) / G; a.gdiv = make_div((uint32_t)a.ngroups);
 	nwg *= a.ngroups;
@@ -2174,12 +2188,18 @@ int rt_packed(RtCall &c)
 	if (c.fp) for (int k = 0; k < C; k++) { a.damp[k] = c.packed->damp[k]; a.boost[k] = c.packed->boost[k]; a.grey_add[k] = c.packed->grey_add[k]; }
 	// --coeff-limit: at or above the block's count nothing is dropped (motion.c:654-657) and the call is the plain one
 	a.keep = c.keep < (size_t)a.nx * a.ny * a.nz ? (unsigned int)c.keep : 0;
+	if (dither) { a.sf = c.dither.sf; a.norm = c.dither.norm; a.slots = packed_dither_slots(a.nz, C, G); }
+	if (dither && !dspfft_block_packed_dither_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_packed_dither.hip)", what);
 	if (!dspfft_block_packed_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_packed.hip)", what);
 	c.nwg = (int)nwg; c.lds = (size_t)G * block_bytes;
 	return 0;
 }
 int rt_run_packed(const RtCall &c)
 {
+	if (c.dither.out8) {
+		if (int rc = dspfft_block_packed_dither_launch(&c.pk, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (%s): backend code %d", kPackedDither, rc);
+		return 0;
+	}
 	if (int rc = dspfft_block_packed_launch(&c.pk, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (%s): backend code %d", kPacked, rc);
 	return 0;
 }
@@ -2249,10 +2269,19 @@ int rt_run_packed_grid(const RtCall &c)
 // [F][h][w][C], run by rt_run_passes with the filter of packed pixels in the middle.  The entry has refused null plans, buffers, d_work and
 // c.packed and f64 plans.  0: the call is ready for rt_run_passes; < 0: it cannot run.  Nothing is launched here.
 constexpr const char *kPackedFrames = "roundtrip on packed 8-bit pixels over full frames";
+constexpr const char *kPackedFramesDither = "dithered roundtrip on packed 8-bit pixels over full frames";
+// the frames of [F][h][w][C] as dspfft_motion_dither_u8_packed takes them: in pixels
+dspfft_dither_geom packed_frames_dither_geom(long long frames, int h, int w)
+{
+	dspfft_dither_geom g = {};
+	g.n[0] = 1; g.n[1] = h; g.n[2] = w; g.row_pitch = w;
+	g.nblocks[0] = (int)frames; g.nblocks[1] = g.nblocks[2] = 1; g.block_step[0] = (long long)h * w;
+	return g;
+}
 int rt_packed_frames(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
-	const char *const what = kPackedFrames;
+	const char *const what = c.dither.out8 ? kPackedFramesDither : kPackedFrames;
 	if (int rc = rt_filter(c, what)) return rc;
 	const int C = c.packed->components;
 	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
@@ -2271,8 +2300,14 @@ int rt_packed_frames(RtCall &c)
 	const long long frame = (long long)h * w * C;
 	if (frame >= (1LL << 32)) return fail(-2, "%s: a frame of 2^32 samples or more", what);
 	rt_trc_ends(c);
-	if (!dspfft_motion_filter_packed || ((c.trc_in.id || c.trc_out.id) && !dspfft_u8_trc_flat_launch))
+	if (!dspfft_motion_filter_packed || ((c.trc_in.id || c.trc_out.id) && !dspfft_u8_trc_flat_launch) || (c.dither.out8 && !dspfft_dither_packed_launch))
 		return fail(-3, "%s: not built into this library (the kernels are HIP-only, motion_filter_packed.hip)", what);
+	if (c.dither.out8) {          // -d: what the dither kernel would refuse after the passes have run is refused here
+		if (frames > 0x7fffffffLL) return fail(-2, "%s: too many frames", what);
+		const dspfft_dither_geom g = packed_frames_dither_geom(frames, h, w);
+		char err[256] = "";
+		if (dspfft_dither_packed_launch(nullptr, nullptr, &g, C, c.dither.sf, c.dither.norm, c.trc_out.id, c.trc_out.tab, 1, c.stream, err, sizeof err)) return fail(-2, "%s: %s", what, err);
+	}
 
 	c.F = &fwd->passes[1]; c.I = &inv->passes[0];
 	c.span = frames * frame;
@@ -2658,7 +2693,14 @@ int roundtrip_core(RtCall &c)
 		if (rc) return rc < 0 ? rc : 0;          // in slices: every slice has stored or dithered its own frames
 		rc = rt_run_passes(c);
 	}
-	if (rc || !c.dither.out8) return rc;
+	if (rc || !c.dither.out8 || c.d_out8) return rc;          // (d_out8 beside dither.out8: packed small blocks, dithered in the kernel's tile)
+	if (c.packed) {
+		const dspfft_dither_geom g = packed_frames_dither_geom(c.pf_frames, c.pf_h, c.pf_w);
+		char err[256] = "";
+		if (dspfft_dither_packed_launch(c.dither.out8, c.d_out, &g, c.packed->components, c.dither.sf, c.dither.norm, c.trc_out.id, c.trc_out.tab, 0, c.stream, err, sizeof err))
+			return fail(-4, "%s", err);
+		return 0;
+	}
 	return dither_store(c.inv, c.d_out, c.dither, c.trc_out, c.stream);
 }
 
@@ -3143,6 +3185,53 @@ extern "C" int dspfft_execute_roundtrip_u8_packed_frames(dspfft_plan fwd, dspfft
 	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.d_out = d_work; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.packed_frames = true;
 	c.coded = d_coeffs_coded; c.stream = stream;
 	return roundtrip_core(c);
+}
+
+// the two packed calls above with motion's -d.  Small blocks: block_packed_dither.hip's kernel stores the bytes itself, so the call carries both
+// d_out8 and c.dither; full frames: the inverse ends as floats in d_work and dspfft_motion_dither_u8_packed's kernels store the bytes
+extern "C" int dspfft_execute_roundtrip_u8_packed_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double scalefactor, double normalization,
+                                                         const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed, const dspfft_coeff_limit *cl,
+                                                         unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", kPackedDither);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", kPackedDither);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", kPackedDither);
+	if (cl && !cl->keep) return fail(-1, "%s: coefficient limit: keep must be at least 1 (pass NULL for no limit)", kPackedDither);
+	if (!(scalefactor > 0) || !(normalization > 0) || !std::isfinite(scalefactor) || !std::isfinite(normalization))
+		return fail(-1, "%s: scalefactor and normalization must be finite and > 0", kPackedDither);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.dither = Dither{d_out, scalefactor, normalization}; c.mul8 = scalefactor * normalization * normalization;
+	c.fp = fp; c.packed = packed; c.coded = d_coeffs_coded; c.stream = stream;
+	if (cl) c.keep = cl->keep;
+	return roundtrip_core(c);
+}
+
+extern "C" int dspfft_execute_roundtrip_u8_packed_frames_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double scalefactor,
+                                                                double normalization, const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed,
+                                                                unsigned long long *d_coeffs_coded, void *stream)
+{
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", kPackedFramesDither);
+	if (!d_work) return fail(-1, "%s: null float work buffer (frames * h * w * components floats)", kPackedFramesDither);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", kPackedFramesDither);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", kPackedFramesDither);
+	if (!(scalefactor > 0) || !(normalization > 0) || !std::isfinite(scalefactor) || !std::isfinite(normalization))
+		return fail(-1, "%s: scalefactor and normalization must be finite and > 0", kPackedFramesDither);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out = d_work; c.dither = Dither{d_out, scalefactor, normalization}; c.fp = fp; c.packed = packed; c.packed_frames = true;
+	c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
+}
+
+// motion_dither.hip's kernels with a pixel step.  Here, not beside dspfft_motion_dither_u8: the CPU emulation library has the entry and answers -3.
+extern "C" int dspfft_motion_dither_u8_packed(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, int components, double scalefactor, double normalization,
+                                              int trc, void *stream)
+{
+	if (components < 2 || components > PACKED_MAX_COMPS) return fail(-1, "dither on packed pixels: components must be 2, 3 or 4 values per pixel, got %d (one component is dspfft_motion_dither_u8)", components);
+	if (trc && !trc_built(trc)) return fail(-1, "dither on packed pixels: the transfer characteristic is not built");
+	if (!dspfft_dither_packed_launch) return fail(-3, "dither on packed pixels: not built into this library (the kernels are HIP-only, motion_dither.hip)");
+	char err[256] = "";
+	if (dspfft_dither_packed_launch(d_pix, d_coeffs, g, components, scalefactor, normalization, trc, nullptr, 0, stream, err, sizeof err)) return fail(-1, "%s", err);
+	return 0;
 }
 
 // ... over a rescaled block grid (rt_packed_grid): out of place, no work buffer, no coefficient limit

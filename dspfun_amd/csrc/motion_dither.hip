@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/dspfft.h"
 #include "dither_core.h"
@@ -48,13 +49,21 @@ __device__ inline long long plane_base(const Geom &g, long long p)
 	return b0 * g.step[0] + b1 * g.step[1] + b2 * g.step[2] + z * g.plane;
 }
 
+// Packed pixels (dspfft_motion_dither_u8_packed): every component of a pixel plane is a plane of its own, its columns `es` elements apart.  row,
+// plane and step count ELEMENTS here (the caller's pixels times es); plane index p = es * (pixel plane) + component.  The planar kernels are
+// the instantiations on Geom, whose element step is the constant 1.
+struct GeomP : Geom { int es; };
+__device__ inline long long plane_base(const GeomP &g, long long p) { return plane_base(static_cast<const Geom &>(g), p / g.es) + p % g.es; }
+__device__ constexpr int elem_step(const Geom &) { return 1; }
+__device__ inline int elem_step(const GeomP &g) { return g.es; }
+
 // --linear (TRC): the function's 256 thresholds lie in LDS behind the error table, and the rings / row errors behind them
 struct TrcArg { const TrcU8Tab *tab; int id; };
 constexpr int kTrcDoubles = 256;
 
 // one lane per plane; 64 lanes per workgroup, their previous-row errors interleaved in LDS (lane-major: no bank conflicts)
-template <bool TRC>
-__device__ __forceinline__ void dither_serial_body(uint8_t *pix, const float *co, Geom g, long long nplanes, double sf, double norm, TrcArg t)
+template <bool TRC, class G>
+__device__ __forceinline__ void dither_serial_body(uint8_t *pix, const float *co, G g, long long nplanes, double sf, double norm, TrcArg t)
 {
 	extern __shared__ double lds[];
 	double *tab = lds, *thr = lds + 256, *dprow = lds + 256 + (TRC ? kTrcDoubles : 0);
@@ -63,24 +72,26 @@ __device__ __forceinline__ void dither_serial_body(uint8_t *pix, const float *co
 	const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (p >= nplanes) return;
 	const long long base = plane_base(g, p);
-	if constexpr (TRC) {
-		const TrcParams tp = trc_params(t.id);
-		dither_plane_serial<true>(pix + base, co + base, g.row, g.h, g.w, sf, norm, tab, dprow + threadIdx.x, blockDim.x, thr, &tp);
-	} else dither_plane_serial(pix + base, co + base, g.row, g.h, g.w, sf, norm, tab, dprow + threadIdx.x, blockDim.x);
+	TrcParams tp;
+	if constexpr (TRC) tp = trc_params(t.id);
+	if constexpr (std::is_same<G, GeomP>::value) dither_plane_step<TRC>(pix + base, co + base, g.row, g.es, g.h, g.w, sf, norm, tab, dprow + threadIdx.x, blockDim.x, thr, &tp);
+	else dither_plane_serial<TRC>(pix + base, co + base, g.row, g.h, g.w, sf, norm, tab, dprow + threadIdx.x, blockDim.x, thr, &tp);
 }
-__global__ __launch_bounds__(64) void dither_serial_kernel(uint8_t *pix, const float *co, Geom g, long long nplanes, double sf, double norm)
+template <class G>
+__global__ __launch_bounds__(64) void dither_serial_kernel(uint8_t *pix, const float *co, G g, long long nplanes, double sf, double norm)
 {
 	dither_serial_body<false>(pix, co, g, nplanes, sf, norm, TrcArg{nullptr, 0});
 }
-__global__ __launch_bounds__(64) void dither_serial_trc_kernel(uint8_t *pix, const float *co, Geom g, long long nplanes, double sf, double norm, TrcArg t)
+template <class G>
+__global__ __launch_bounds__(64) void dither_serial_trc_kernel(uint8_t *pix, const float *co, G g, long long nplanes, double sf, double norm, TrcArg t)
 {
 	dither_serial_body<true>(pix, co, g, nplanes, sf, norm, t);
 }
 
 struct WaveSched { int nw, D, R, L; };   // waves, band-to-band offset, ring length, steps per band (a multiple of kChunk)
 
-template <bool TRC>
-__device__ __forceinline__ void dither_wave_body(uint8_t *pix, const float *co, Geom g, WaveSched s, double sf, double norm, TrcArg t)
+template <bool TRC, class G>
+__device__ __forceinline__ void dither_wave_body(uint8_t *pix, const float *co, G g, WaveSched s, double sf, double norm, TrcArg t)
 {
 	extern __shared__ double lds[];
 	double *tab = lds, *thr = lds + 256, *rings = lds + 256 + (TRC ? kTrcDoubles : 0);
@@ -90,7 +101,7 @@ __device__ __forceinline__ void dither_wave_body(uint8_t *pix, const float *co, 
 	TrcParams tp;
 	if constexpr (TRC) tp = trc_params(t.id);
 	const long long base = plane_base(g, blockIdx.x);
-	const int h = g.h, w = g.w, nbands = (h + 63) >> 6;
+	const int h = g.h, w = g.w, nbands = (h + 63) >> 6, es = elem_step(g);
 	const long long total = (long long)(nbands - 1) * s.D + s.L;
 	int band = -1;
 	// lane state: the window dp(r-1, x-1 .. x+1), the error handed down for the next step, the left neighbour's error, ring slots
@@ -127,14 +138,14 @@ __device__ __forceinline__ void dither_wave_body(uint8_t *pix, const float *co, 
 #pragma unroll
 			for (int i = 0; i < kChunk; i++) {
 				const int x = x0 + i;
-				v[i] = have_next ? vn[i] : (rowok && x >= 0 && x < w) ? co[rowoff + x] : 0.f;
+				v[i] = have_next ? vn[i] : (rowok && x >= 0 && x < w) ? co[rowoff + (long long)x * es] : 0.f;
 			}
 			have_next = t0 + kChunk < s.L;
 			if (have_next) {
 #pragma unroll
 				for (int i = 0; i < kChunk; i++) {
 					const int x = x0 + kChunk + i;
-					vn[i] = (rowok && x >= 0 && x < w) ? co[rowoff + x] : 0.f;
+					vn[i] = (rowok && x >= 0 && x < w) ? co[rowoff + (long long)x * es] : 0.f;
 				}
 			}
 #pragma unroll
@@ -155,17 +166,19 @@ __device__ __forceinline__ void dither_wave_body(uint8_t *pix, const float *co, 
 #pragma unroll
 			for (int i = 0; i < kChunk; i++) {
 				const int x = x0 + i;
-				if (rowok && x >= 0 && x < w) pix[rowoff + x] = ob[i];
+				if (rowok && x >= 0 && x < w) pix[rowoff + (long long)x * es] = ob[i];
 			}
 		}
 		__syncthreads();
 	}
 }
-__global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_kernel(uint8_t *pix, const float *co, Geom g, WaveSched s, double sf, double norm)
+template <class G>
+__global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_kernel(uint8_t *pix, const float *co, G g, WaveSched s, double sf, double norm)
 {
 	dither_wave_body<false>(pix, co, g, s, sf, norm, TrcArg{nullptr, 0});
 }
-__global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_trc_kernel(uint8_t *pix, const float *co, Geom g, WaveSched s, double sf, double norm, TrcArg t)
+template <class G>
+__global__ __launch_bounds__(kMaxWaves * 64) void dither_wave_trc_kernel(uint8_t *pix, const float *co, G g, WaveSched s, double sf, double norm, TrcArg t)
 {
 	dither_wave_body<true>(pix, co, g, s, sf, norm, t);
 }
@@ -194,11 +207,28 @@ int dbad(char *err, size_t len, const char *m) { if (err && len) snprintf(err, l
 
 }  // namespace
 
-// trc = 0: the plain store; else tab points at the function's tables on the device
-static int dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp, double scalefactor, double normalization, int trc, const void *tab,
-                         void *stream, char *err, size_t errlen)
+// the two regimes' launches on a geometry: Geom (planar) or GeomP (packed pixels)
+template <class G>
+static void dither_launch_serial(uint8_t *d_pix, const float *d_coeffs, const G &g, long long nplanes, size_t lds, double sf, double norm, const TrcArg &ta, hipStream_t st)
 {
-	if (!d_pix || !d_coeffs || !gp) return dbad(err, errlen, "dither: null pointer");
+	const unsigned nwg = (unsigned)((nplanes + 63) / 64);
+	if (ta.id) hipLaunchKernelGGL(dither_serial_trc_kernel<G>, dim3(nwg), dim3(64), lds, st, d_pix, d_coeffs, g, nplanes, sf, norm, ta);
+	else hipLaunchKernelGGL(dither_serial_kernel<G>, dim3(nwg), dim3(64), lds, st, d_pix, d_coeffs, g, nplanes, sf, norm);
+}
+template <class G>
+static void dither_launch_wave(uint8_t *d_pix, const float *d_coeffs, const G &g, long long nplanes, const WaveSched &s, size_t lds, double sf, double norm, const TrcArg &ta,
+                               hipStream_t st)
+{
+	if (ta.id) hipLaunchKernelGGL(dither_wave_trc_kernel<G>, dim3((unsigned)nplanes), dim3(64 * s.nw), lds, st, d_pix, d_coeffs, g, s, sf, norm, ta);
+	else hipLaunchKernelGGL(dither_wave_kernel<G>, dim3((unsigned)nplanes), dim3(64 * s.nw), lds, st, d_pix, d_coeffs, g, s, sf, norm);
+}
+
+// trc = 0: the plain store; else tab points at the function's tables on the device.  comps = 0: planar buffers; 2..4: packed pixels, *gp in
+// pixels.  dry: every check, no launch (the buffers are then not looked at).
+static int dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp, int comps, double scalefactor, double normalization, int trc, const void *tab,
+                         void *stream, char *err, size_t errlen, bool dry = false)
+{
+	if ((!dry && (!d_pix || !d_coeffs)) || !gp) return dbad(err, errlen, "dither: null pointer");
 	const dspfft_dither_geom &q = *gp;
 	if (q.n[0] < 1 || q.n[1] < 1 || q.n[2] < 1 || q.nblocks[0] < 1 || q.nblocks[1] < 1 || q.nblocks[2] < 1) return dbad(err, errlen, "dither: extents and block counts must be >= 1");
 	if ((q.n[1] > 1 && q.row_pitch < q.n[2]) || (q.n[0] > 1 && q.plane_pitch < 1) || q.row_pitch < 0 || q.plane_pitch < 0 ||
@@ -208,22 +238,28 @@ static int dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dit
 	Geom g;
 	g.d = q.n[0]; g.h = q.n[1]; g.w = q.n[2]; g.row = q.n[1] > 1 ? q.row_pitch : q.n[2]; g.plane = q.plane_pitch;
 	for (int i = 0; i < 3; i++) { g.nb[i] = q.nblocks[i]; g.step[i] = q.block_step[i]; }
-	const long long nplanes = (long long)g.d * g.nb[0] * g.nb[1] * g.nb[2];
+	const int es = comps ? comps : 1;
+	const long long nplanes = (long long)g.d * g.nb[0] * g.nb[1] * g.nb[2] * es;
+	GeomP gq;
+	static_cast<Geom &>(gq) = g;
+	gq.es = es; gq.row *= es; gq.plane *= es;
+	for (int i = 0; i < 3; i++) gq.step[i] *= es;
 	hipStream_t st = (hipStream_t)stream;
 	const TrcArg ta = {(const TrcU8Tab *)tab, trc};
 	if (small_plane(g.h, g.w)) {
 		const size_t lds = (256 + (trc ? kTrcDoubles : 0) + 64 * (size_t)g.w) * sizeof(double);
-		const long long nwg = (nplanes + 63) / 64;
-		if (nwg >= (1ll << 31)) return dbad(err, errlen, "dither: too many planes");
-		if (trc) hipLaunchKernelGGL(dither_serial_trc_kernel, dim3((unsigned)nwg), dim3(64), lds, st, d_pix, d_coeffs, g, nplanes, scalefactor, normalization, ta);
-		else hipLaunchKernelGGL(dither_serial_kernel, dim3((unsigned)nwg), dim3(64), lds, st, d_pix, d_coeffs, g, nplanes, scalefactor, normalization);
+		if ((nplanes + 63) / 64 >= (1ll << 31)) return dbad(err, errlen, "dither: too many planes");
+		if (dry) return 0;
+		if (comps) dither_launch_serial(d_pix, d_coeffs, gq, nplanes, lds, scalefactor, normalization, ta, st);
+		else dither_launch_serial(d_pix, d_coeffs, g, nplanes, lds, scalefactor, normalization, ta, st);
 	} else {
 		const WaveSched s = wave_sched(g.h, g.w, wave_limit());
 		const size_t lds = (256 + (trc ? kTrcDoubles : 0) + (size_t)(s.nw + 1) * s.R) * sizeof(double);
 		if (lds > kMaxLds) return dbad(err, errlen, "dither: plane too wide for the wavefront kernel's LDS rings (w above about 9000)");
 		if (nplanes >= (1ll << 31)) return dbad(err, errlen, "dither: too many planes");
-		if (trc) hipLaunchKernelGGL(dither_wave_trc_kernel, dim3((unsigned)nplanes), dim3(64 * s.nw), lds, st, d_pix, d_coeffs, g, s, scalefactor, normalization, ta);
-		else hipLaunchKernelGGL(dither_wave_kernel, dim3((unsigned)nplanes), dim3(64 * s.nw), lds, st, d_pix, d_coeffs, g, s, scalefactor, normalization);
+		if (dry) return 0;
+		if (comps) dither_launch_wave(d_pix, d_coeffs, gq, nplanes, s, lds, scalefactor, normalization, ta, st);
+		else dither_launch_wave(d_pix, d_coeffs, g, nplanes, s, lds, scalefactor, normalization, ta, st);
 	}
 	return hipGetLastError() == hipSuccess ? 0 : dbad(err, errlen, "dither: kernel launch failed");
 }
@@ -232,7 +268,7 @@ static int dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dit
 extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp,
                                                                            double scalefactor, double normalization, void *stream, char *err, size_t errlen)
 {
-	return dither_launch(d_pix, d_coeffs, gp, scalefactor, normalization, 0, nullptr, stream, err, errlen);
+	return dither_launch(d_pix, d_coeffs, gp, 0, scalefactor, normalization, 0, nullptr, stream, err, errlen);
 }
 // --linear: trc is a built id (engine.cpp has checked it); tab: a plan's device tables, or NULL for motion_ops.hip's own
 extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_trc_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp, double scalefactor,
@@ -240,7 +276,16 @@ extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_trc_launch(ui
 {
 	if (!tab) tab = dspfft_u8_trc_cached_tab(trc);
 	if (!tab) return dbad(err, errlen, "dither: the transfer characteristic's tables could not be uploaded");
-	return dither_launch(d_pix, d_coeffs, gp, scalefactor, normalization, trc, tab, stream, err, errlen);
+	return dither_launch(d_pix, d_coeffs, gp, 0, scalefactor, normalization, trc, tab, stream, err, errlen);
+}
+// packed pixels (dspfft_motion_dither_u8_packed; engine.cpp has checked comps and trc).  trc = 0: plain; tab as above.  dry: the checks alone,
+// for a caller that must refuse before it launches anything
+extern "C" __attribute__((visibility("hidden"))) int dspfft_dither_packed_launch(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *gp, int comps, double scalefactor,
+                                                                                  double normalization, int trc, const void *tab, int dry, void *stream, char *err, size_t errlen)
+{
+	if (trc && !tab && !dry) tab = dspfft_u8_trc_cached_tab(trc);
+	if (trc && !tab && !dry) return dbad(err, errlen, "dither: the transfer characteristic's tables could not be uploaded");
+	return dither_launch(d_pix, d_coeffs, gp, comps, scalefactor, normalization, trc, tab, stream, err, errlen, dry != 0);
 }
 
 extern "C" int dspfft_motion_dither_u8(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor, double normalization, void *stream)

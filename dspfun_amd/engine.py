@@ -283,6 +283,23 @@ class Plan:
         self._check(self._lib.dspfft_execute_roundtrip_u8_packed_frames(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work or None),
                                                                         float(out_mul), *self._tail(filter, d_coded, stream, pk)))
 
+    def roundtrip_u8_packed_dither(self, inv, d_in_u8, d_out_u8, scalefactor, normalization, packed, filter=None, coeff_limit=0, d_coded=0, stream=0):
+        """dspfft_execute_roundtrip_u8_packed_dither: roundtrip_u8_packed with motion's -d, one launch -- the Floyd-Steinberg store runs in the
+        kernel's LDS tile.  Arguments as roundtrip_u8_packed's, with info["scalefactor"] and info["normalization"] in place of out_mul.  The
+        bytes are roundtrip_u8_dither's on each component's plane.  Needs no work buffer; may run in place."""
+        cl = self._coeff_limit(inv, coeff_limit, work=False)[0] if coeff_limit else None
+        between = (C.byref(packed) if packed is not None else None, C.byref(cl) if cl is not None else None)
+        self._check(self._lib.dspfft_execute_roundtrip_u8_packed_dither(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(scalefactor),
+                                                                        float(normalization), *self._tail(filter, d_coded, stream, *between)))
+
+    def roundtrip_u8_packed_frames_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, packed, filter=None, d_coded=0, stream=0):
+        """dspfft_execute_roundtrip_u8_packed_frames_dither: roundtrip_u8_packed_frames with motion's -d -- the inverse ends as floats in
+        d_work (which keeps them) and motion_dither_u8_packed's kernels store the bytes.  Arguments as roundtrip_u8_packed_frames's, with
+        info["scalefactor"] and info["normalization"] in place of out_mul.  May run in place."""
+        pk = C.byref(packed) if packed is not None else None
+        self._check(self._lib.dspfft_execute_roundtrip_u8_packed_frames_dither(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), C.c_void_p(d_work or None),
+                                                                               float(scalefactor), float(normalization), *self._tail(filter, d_coded, stream, pk)))
+
     def roundtrip_u8_dither(self, inv, d_in_u8, d_out_u8, d_work, scalefactor, normalization, filter=None, d_coded=0, stream=0,
                             coeff_limit=0, outside_mul=1.0, topn_work=None):
         """roundtrip_u8 with motion's -d (motion.c:756-788): the last inverse pass leaves floats in d_work and the bytes are the
@@ -533,6 +550,23 @@ def motion_dither_u8(d_pix, d_coeffs, n, row_pitch=None, plane_pitch=None, nbloc
         rc = lib.dspfft_motion_dither_u8(C.c_void_p(d_pix), C.c_void_p(d_coeffs), C.byref(g), float(scalefactor), float(normalization), C.c_void_p(stream))
     if rc:
         raise DspfftError(lib.dspfft_motion_last_error().decode())
+
+
+def motion_dither_u8_packed(d_pix, d_coeffs, n, components, row_pitch=None, plane_pitch=None, nblocks=(1, 1, 1), block_step=(0, 0, 0), scalefactor=1.0,
+                            normalization=1.0, stream=0, lib=None, trc=0):
+    """dspfft_motion_dither_u8_packed: motion_dither_u8 over buffers of `components` values per pixel, every component a plane of its own.
+    n, the pitches and the block steps count PIXELS, as motion_dither_u8's; the element of component c is at components * (pixel offset) + c."""
+    lib = lib or _lib.load()
+    n = [int(v) for v in n]
+    g = _lib.DitherGeom()
+    g.n[:] = n
+    g.row_pitch = n[2] if row_pitch is None else int(row_pitch)
+    g.plane_pitch = n[1] * g.row_pitch if plane_pitch is None else int(plane_pitch)
+    g.nblocks[:] = [int(v) for v in nblocks]
+    g.block_step[:] = [int(v) for v in block_step]
+    if lib.dspfft_motion_dither_u8_packed(C.c_void_p(d_pix), C.c_void_p(d_coeffs), C.byref(g), int(components), float(scalefactor), float(normalization),
+                                          trc_id(trc, lib), C.c_void_p(stream)):
+        raise DspfftError(lib.dspfft_last_error().decode())
 
 
 def motion_topn_blocks(t, count, keep, stride=None, stream=None, lib=None):

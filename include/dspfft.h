@@ -420,8 +420,9 @@ int dspfft_execute_roundtrip_u8_dither_limit(dspfft_plan fwd, dspfft_plan inv, c
  * uses no work buffer.  Nothing is launched when it fails:
  *   -1  a NULL plan, buffer or `packed`; an f64 plan; cl with keep == 0; bad filter parameters
  *   -2  components outside 2..4; a pair the fused block pass does not take (per-frame plans, one 3-D block); different extents in fwd and
- *       inv (a rescaled grid, motion -s: that pair is dspfft_execute_roundtrip_u8_packed_rescale's, below; -d and --spectrogram /
- *       --ispectrogram are not implemented on packed small blocks); buffers off 4 bytes; a block whose `components` tiles plus the tables do not fit one workgroup's 64 KB of LDS -- of the listed extents that is
+ *       inv (a rescaled grid, motion -s: that pair is dspfft_execute_roundtrip_u8_packed_rescale's, below; -d is
+ *       dspfft_execute_roundtrip_u8_packed_dither's and --spectrogram / --ispectrogram are dspfft_execute_spectrogram_u8_packed's /
+ *       _ispectrogram_u8_packed's, all below); buffers off 4 bytes; a block whose `components` tiles plus the tables do not fit one workgroup's 64 KB of LDS -- of the listed extents that is
  *       16 x 16 x 16 at four components --; more than 2^31 - 1 workgroups
  *   -3  a library built without the HIP kernel */
 typedef struct {
@@ -493,11 +494,50 @@ int dspfft_execute_roundtrip_u8_packed_rescale(dspfft_plan fwd, dspfft_plan inv,
  *       dspfft_execute_roundtrip_u8_packed); rank 3 (one 3-D block, -b 0x0x0); different extents in fwd and inv (-s); a pair that is not the
  *       dense in-place layout above with REDFT10 in fwd, REDFT01 in inv and inv running its column pass first; a frame of 2^32 samples or more
  *   -3  a library built without the HIP kernels
- * Not implemented on packed full frames, each refused where a call could ask for it: -d (the dither kernels have no pixel step),
- * --coeff-limit (a component's frame is no contiguous run: this entry takes no limit), -s, one 3-D block, float and padded (rgb0) formats. */
+ * -d is dspfft_execute_roundtrip_u8_packed_frames_dither's (below).  Not implemented on packed full frames, each refused where a call could
+ * ask for it: --coeff-limit (a component's frame is no contiguous run: this entry takes no limit), -s, one 3-D block, float and padded (rgb0) formats. */
 int dspfft_execute_roundtrip_u8_packed_frames(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double out_mul,
                                               const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
                                               unsigned long long *d_coeffs_coded, void *hip_stream);
+
+/* dspfft_execute_roundtrip_u8_packed with motion's -d (motion -b 8x8x8 -q 20 -d on rgb24: motion.c:778-787 inside the loop over components,
+ * :613-615): that entry's contract in every respect but the store -- the same planar small-block pair, 2, 3 or 4 components, per-byte damp / boost
+ * / grey_add, cl, dspfft_plan_set_u8_trc at either end (the dithered byte is then the encoded one, as in dspfft_motion_dither_u8_trc), in place
+ * allowed, stream-ordered, no allocation and NO work buffer.  scalefactor and normalization replace out_mul (= scalefactor normalization^2), as in
+ * dspfft_execute_roundtrip_u8_dither: the error of a pixel is c - byte / (normalization^2 scalefactor).
+ * ONE kernel (block_packed_dither.hip), no float intermediate: when the inverse's y pass ends, the z planes of a tile's component blocks are the
+ * planes of the Floyd-Steinberg store and lie in LDS whole.  The inverse's x pass writes its floats back to the tile (bit for bit what the planar
+ * dithered call leaves in d_work), one thread per plane walks it in raster order (dither_core.h: the arithmetic and its precision contract are
+ * dspfft_motion_dither_u8's) leaving each byte where its float was, and the bytes leave through the packed store: 2 * components bytes per pixel.
+ * The bytes EQUAL those of dspfft_execute_roundtrip_u8_dither (with cl: _dither_limit) on the same pair on each component's plane with that
+ * component's damp, boost and grey_add, and d_coeffs_coded the sum of the planar counts.
+ * A plane is a dependent chain of NY NX steps in double on one lane, so blocks with few, large planes (1 x 32 x 32) leave most of a workgroup
+ * idle during the dither; measured only on 8 x 8 x 8 and 1 x 8 x 8 blocks (profiles/r22_motion_packed_dither.txt).
+ * Nothing is launched when it fails: dspfft_execute_roundtrip_u8_packed's codes and reasons under this entry's name, and
+ *   -1  scalefactor or normalization not finite or not > 0
+ *   -2  a tile whose component blocks, tables, error table (2 KB) and error rows (NX doubles per dither lane) do not fit 64 KB of LDS;
+ *       different extents in fwd and inv: -d on a packed rescaled grid is not implemented (its tile keeps only min(block, scaled) columns and
+ *       has no room for the scaled planes)
+ *   -3  a library built without the HIP kernel
+ * Not implemented with -d on packed pixels: a rescaled grid, one 3-D block, float and padded (rgb0) formats. */
+int dspfft_execute_roundtrip_u8_packed_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double scalefactor, double normalization,
+                                              const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                              const dspfft_coeff_limit *cl /* NULL: no --coeff-limit */,
+                                              unsigned long long *d_coeffs_coded, void *hip_stream);
+
+/* dspfft_execute_roundtrip_u8_packed_frames with motion's -d: the same pair, buffers, filter and sequence up to the last inverse pass -- the
+ * fused packed column roundtrip, the unfused sequence (DSPFFT_NO_FUSED_ROUNDTRIP=1) and the quantiser-only shortcut are taken as there --, but the
+ * inverse row pass writes FLOAT into d_work (no 8-bit row end, no dspfft_f32_to_u8) and dspfft_motion_dither_u8_packed (below) over
+ * [F][H][W][C] -- n = {1, H, W}, nblocks = {F, 1, 1}, block_step = {H W} -- writes the bytes.  d_work afterwards holds what was dithered.
+ * A transfer characteristic on `inv` is applied by the dither's trc variant, one on `fwd` by the flat sweep as in the undithered call.
+ * d_in == d_out is allowed.  The floats in d_work and the coded count EQUAL those of the composition dspfft_u8_to_f32 -> dspfft_execute(fwd) ->
+ * dspfft_motion_filter_packed -> dspfft_execute(inv), and the bytes those of dspfft_motion_dither_u8_packed over them.
+ * Nothing is launched when it fails: the undithered entry's codes and reasons under this entry's name, and
+ *   -1  scalefactor or normalization not finite or not > 0
+ *   -2  what dspfft_motion_dither_u8_packed refuses of the frames, with its reason: a width above the wavefront kernel's LDS rings (about 9000) */
+int dspfft_execute_roundtrip_u8_packed_frames_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, float *d_work, double scalefactor,
+                                                     double normalization, const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                                     unsigned long long *d_coeffs_coded, void *hip_stream);
 
 /* motion --spectrogram and --ispectrogram (motion/motion.c:617-776 with `spec` / `ispec` set) as one call per clip: the two halves of
  * the roundtrip above, each with ONE plan.
@@ -865,6 +905,13 @@ int dspfft_motion_dither_u8(uint8_t *d_pix, const float *d_coeffs, const dspfft_
  * linear coefficient, and so does this).  Byte-identical to the reference's lines built F / D with linear = true.  -1 for a trc that is 0 or
  * not built. */
 int dspfft_motion_dither_u8_trc(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, double scalefactor, double normalization, int trc, void *hip_stream);
+/* The two calls above on PACKED pixels: d_pix and d_coeffs hold `components` (2, 3 or 4) values per pixel, every component of a pixel plane is
+ * a plane of its own (motion.c:613-615), and there are `components` times as many planes.  g is in PIXELS exactly as above: the element of
+ * component c is at components * (the pixel offset above) + c.  The same two kernels with an element step, the regime chosen from the plane's
+ * extent in pixels as above.  trc = 0: the plain byte; else the encoded one (dspfft_motion_dither_u8_trc).  -1 for components outside 2..4 and
+ * for everything the planar call refuses; -3 from a library built without the HIP kernels; the reason in dspfft_last_error. */
+int dspfft_motion_dither_u8_packed(uint8_t *d_pix, const float *d_coeffs, const dspfft_dither_geom *g, int components, double scalefactor, double normalization,
+                                   int trc /* 0: plain */, void *hip_stream);
 /* motion.c:652-668 (--coeff-limit): keep the `keep` coefficients of largest magnitude among d_coeffs[0 .. count), zero the rest.
  * Radix select on the device (four histogram passes over the bits of |c|, no sort).  Ties at the threshold: the reference's choice
  * depends on qsort; here the earliest in buffer order are kept -- documented, deterministic. */
