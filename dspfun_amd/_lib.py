@@ -27,7 +27,7 @@ SYMBOLS = [
     "dspfft_execute_spectrogram_u8_packed", "dspfft_execute_ispectrogram_u8_packed", "dspfft_motion_spec_blocks_u8_packed", "dspfft_motion_ispec_blocks_u8_packed",
     "dspfft_plan_guru_r2r_ordered",
     "dspfft_execute","dspfft_plan_num_passes", "dspfft_execute_pass", "dspfft_destroy_plan", "dspfft_plan_describe", "dspfft_plan_algorithmic_bytes",
-    "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_many_fused_pairs", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_execute_n", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
+    "dspfft_execute_many", "dspfft_execute_many_repeat", "dspfft_many_fused_pairs", "dspfft_col_roundtrip_table_bytes", "dspfft_col_roundtrip_launches", "dspfft_execute_sum2", "dspfft_cosrows_create", "dspfft_cosrows_execute", "dspfft_cosrows_destroy", "dspfft_cztrows_create", "dspfft_cztrows_execute", "dspfft_cztrows_execute_n", "dspfft_cztrows_length", "dspfft_cztrows_destroy", "dspfft_transpose_f32", "dspfft_plan_set_input_modulation", "dspfft_stream_create", "dspfft_stream_destroy", "dspfft_stream_synchronize", "dspfft_event_create", "dspfft_event_destroy", "dspfft_event_synchronize", "dspfft_event_elapsed_ms",
     "dspfft_last_error", "dspfft_version", "dspfft_set_thread_plan_effort", "dspfft_get_thread_plan_effort", "dspfft_fftw_sparse_uploads",
     "dspfft_scan_zigzag", "dspfft_scan_zigzag_frame_ids", "dspfft_execute_masked_accumulate", "dspfft_execute_masked_accumulate_range", "dspfft_execute_masked_accumulate_range_f64", "dspfft_scan_scatter", "dspfft_accumulate", "dspfft_broadcast_dc",
     "dspfft_scan_limit", "dspfft_scan_max_interval", "dspfft_scan_coord_slots", "dspfft_scan_owner_index", "dspfft_scan_frame_ids", "dspfft_scan_coords", "dspfft_scan_stamp",
@@ -131,6 +131,12 @@ def bind(lib):
     if hasattr(lib, "dspfft_many_fused_pairs"):     # (absent from a build of an earlier commit named by DSPFFT_LIB_PATH for an A/B run)
         lib.dspfft_many_fused_pairs.restype = C.c_ulonglong
         lib.dspfft_many_fused_pairs.argtypes = []
+    if hasattr(lib, "dspfft_col_roundtrip_table_bytes"):
+        lib.dspfft_col_roundtrip_table_bytes.restype = C.c_longlong
+        lib.dspfft_col_roundtrip_table_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    if hasattr(lib, "dspfft_col_roundtrip_launches"):
+        lib.dspfft_col_roundtrip_launches.restype = C.c_ulonglong
+        lib.dspfft_col_roundtrip_launches.argtypes = []
     lib.dspfft_stream_create.restype = vp
     lib.dspfft_stream_create.argtypes = []
     lib.dspfft_stream_destroy.argtypes = [vp]

@@ -871,6 +871,47 @@ struct ColSpecT {
 	static constexpr int LAST_ROUNDS = (NBL * NP + T - 1) / T;
 	static constexpr int Y_ROUNDS = (N * NP + T - 1) / T;              // REDFT10: (row, lane vector) items per thread
 	static constexpr int K_ROUNDS = ((N / 2 + 1) * NP + T - 1) / T;    // REDFT01: (k, lane vector) items per thread
+	// ---- the fused roundtrip's twiddle tables behind the tile (spec_fused.h) ----
+	// What the fused kernel reads of W and T: W[m TW], m < M1, of every stage with M1 > 1, one stage after the other, then T[k], k <= N/2.
+	// A workgroup copies them into the LDS its tile leaves free, so that the five twiddled phases (two forward stages, mid_read, two
+	// inverse stages on the 2160-row tile) open with an LDS read instead of a cache round trip behind their barrier.  Only where that
+	// costs no resident workgroup (RT_TABLES); elsewhere the kernel keeps its global loads.  Decided here, at compile time.
+	template <int I> static constexpr int stage_m1() { return pack_lc<I, Rs...>() / pack_get<I, Rs...>(); }
+	template <int I> static constexpr int rt_tab_off() { if constexpr (I <= 0) return 0; else return rt_tab_off<I - 1>() + (stage_m1<I - 1>() > 1 ? stage_m1<I - 1>() : 0); }
+	static constexpr int RT_TAB_W = rt_tab_off<NS>();                  // entries of W (all stages), = where T starts
+	static constexpr int RT_TAB_N = RT_TAB_W + N / 2 + 1;
+	static constexpr size_t RT_TAB_BYTES = (size_t)RT_TAB_N * sizeof(CX);
+	// workgroups a CU's 160 KB holds at `bytes` of tile (+ tables): with the fused kernel's static block in front (its count of coded
+	// coefficients, padded to the tile's 32-byte alignment), in the 1280-byte granules LDS is allocated in on gfx950
+	static constexpr size_t RT_LDS_STATIC = 32, RT_LDS_GRANULE = 1280;
+	static constexpr int rt_resident(size_t bytes) { return (int)((160 * 1024) / ((bytes + RT_LDS_STATIC + RT_LDS_GRANULE - 1) / RT_LDS_GRANULE * RT_LDS_GRANULE)); }
+	static constexpr bool RT_TABLES = rt_resident(LDS + RT_TAB_BYTES) == rt_resident(LDS);
+	static constexpr size_t RT_LDS = LDS + (RT_TABLES ? RT_TAB_BYTES : 0);   // what the fused kernel asks for: tile + tables
+	static constexpr int RT_TAB_ROUNDS = (RT_TAB_N + T - 1) / T;
+	// table entry e as the plan's tables hold it (e < RT_TAB_N)
+	static DSP_HD const CX *rt_tab_src(const PA &a, int e)
+	{
+		const CX *p = a.T + (e - RT_TAB_W);
+		static_for<0, NS>([&](auto i) {
+			constexpr int M1 = stage_m1<i>(), TW = N / pack_lc<i, Rs...>(), O = rt_tab_off<i>();
+			if constexpr (M1 > 1) { if (e >= O && e < O + M1) p = a.W + (e - O) * TW; }
+		});
+		return p;
+	}
+	static DSP_HD void rt_tab_fetch(const PA &a, int tid, CX (&r)[RT_TAB_ROUNDS])
+	{
+		static_for<0, RT_TAB_ROUNDS>([&](auto j) {
+			const int e = tid + j * T;
+			if ((j + 1) * T <= RT_TAB_N || e < RT_TAB_N) r[j] = *rt_tab_src(a, e);
+		});
+	}
+	static DSP_HD void rt_tab_put(CX *tab, int tid, const CX (&r)[RT_TAB_ROUNDS])
+	{
+		static_for<0, RT_TAB_ROUNDS>([&](auto j) {
+			const int e = tid + j * T;
+			if ((j + 1) * T <= RT_TAB_N || e < RT_TAB_N) tab[e] = r[j];
+		});
+	}
 	template <int KIND> struct State {
 		LC x[LAST_ROUNDS * RL];
 		LC pre[KIND == KIND_REDFT10 ? Y_ROUNDS : 2 * K_ROUNDS];   // the loaded rows, column order (g_get)
@@ -1030,8 +1071,9 @@ struct ColSpecT {
 		bout = i0 * a.sb0_out + i1 * a.sb1_out + (long long)t * K;
 	}
 
-	template <int I>
-	static DSP_HD void stage(const PA &a, V *buf, int tid)
+	// LT: the stage twiddle comes from the fused roundtrip's table in LDS (tab, rt_tab_off) instead of the plan's W
+	template <int I, bool LT = false>
+	static DSP_HD void stage(const PA &a, V *buf, int tid, const CX *tab = nullptr)
 	{
 		constexpr int R = pack_get<I, Rs...>(), Lc = pack_lc<I, Rs...>(), M1 = Lc / R, NB = N / R, TW = N / Lc;
 		tloop<NB * NP, T>(tid, [&](int it) {
@@ -1046,7 +1088,7 @@ struct ColSpecT {
 			Dft<R>::run(x);
 			if constexpr (M1 > 1) {
 				CX w[R];
-				w[1] = a.W[m * TW];
+				if constexpr (LT) w[1] = tab[rt_tab_off<I>() + m]; else w[1] = a.W[m * TW];
 				static_for<2, R>([&](auto r) { if constexpr (r % 2 == 0) w[r] = csqr(w[r / 2]); else w[r] = cmul(w[r / 2], w[r - r / 2]); });
 				static_for<1, R>([&](auto r) { x[r] = lmul(x[r], w[r]); });
 			}
@@ -1123,8 +1165,8 @@ struct ColSpecT {
 		CX tw[1];
 	};
 	struct StateMid { LC pre[2 * K_ROUNDS]; };      // what mid_read hands mid_write (spec_fused.h: one state object per transform)
-	template <class ST, class F>
-	static DSP_HD void mid_read(const PA &af, const PA &ai, const V *buf, long long bout, int tid, ST &st, const F &filt, unsigned long long &coded)
+	template <class ST, class F, bool LT = false>
+	static DSP_HD void mid_read(const PA &af, const PA &ai, const V *buf, long long bout, int tid, ST &st, const F &filt, unsigned long long &coded, const CX *tab = nullptr)
 	{
 		static_for<0, K_ROUNDS>([&](auto ri) {
 			const int it = tid + ri * T;
@@ -1132,7 +1174,8 @@ struct ColSpecT {
 			const int k = it / NP, jp = it - k * NP;
 			const int km = k ? N - k : 0;
 			const LC zk = l_get(buf[k * NP + jp]), zm = l_get(buf[km * NP + jp]);
-			const CX t = af.T[k];
+			CX t;
+			if constexpr (LT) t = tab[RT_TAB_W + k]; else t = af.T[k];
 			const Re sc = af.scale, s0 = (k == 0) ? sc * af.out_scale0 : sc;
 			const long long o = bout + VW * jp;
 			LC r0, r1;
@@ -1166,8 +1209,8 @@ struct ColSpecT {
 		});
 	}
 
-	template <int KIND, int PH, class ST>
-	static DSP_HD void phase(const PA &a, V *buf, long long bout, int tid, ST &st)
+	template <int KIND, int PH, class ST, bool LT = false>
+	static DSP_HD void phase(const PA &a, V *buf, long long bout, int tid, ST &st, const CX *tab = nullptr)
 	{
 		if constexpr (PH == 0) {
 			if constexpr (KIND == KIND_REDFT10) {
@@ -1196,7 +1239,7 @@ struct ColSpecT {
 				});
 			}
 		} else if constexpr (PH < NS) {
-			stage<PH - 1>(a, buf, tid);
+			stage<PH - 1, LT>(a, buf, tid, tab);
 		} else if constexpr (PH == NS) {
 			if (KIND == KIND_REDFT01 && lean01(a)) last_store01(a, buf, bout, tid); else last_read(buf, st, tid);
 		} else if constexpr (PH == NS + 1) {

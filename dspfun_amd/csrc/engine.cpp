@@ -37,6 +37,8 @@
 #include "block_spec_packed_core.h"
 #include "trc_u8_core.h"
 #include "spec_image_core.h"
+#include "dct_spec.h"
+#include "spec_list.h"
 
 using namespace dspfft;
 
@@ -2469,6 +2471,9 @@ int rt_run_rescale(const RtCall &c)
 	return 0;
 }
 
+// fused column launches this process has enqueued so far (listed, packed twin or compiled at plan time): tests tell the fused path from the
+// unfused sequence by it, since the results are the same bits
+std::atomic<unsigned long long> g_col_roundtrip_launches{0};
 // Whether rt_run_passes runs the forward plan's last pass and the inverse plan's first as ONE column kernel, and that kernel's arguments: both
 // are COL passes with the same listed kernel (or kernels compiled at plan time for the same type) over the same tiles, plain, without a host
 // loop, on 16-byte-aligned buffers, and nothing has to see the whole spectrum in between.  `src` is what the forward plan's last pass reads.
@@ -2514,6 +2519,7 @@ int rt_run_passes(const RtCall &c)
 	PassArgs af, ai;
 	bool compiled;
 	if (rt_col_fused(c, src, af, ai, compiled)) {
+		g_col_roundtrip_launches.fetch_add(1, std::memory_order_relaxed);
 		if (compiled) {
 			// parameters: (PassArgs af, PassArgs ai, FilterOp filt, unsigned long long *coded); FilterOp is the MotionFilter, nothing else
 			void *args[4] = {&af, &ai, (void *)&c.mf, (void *)&c.coded};
@@ -3305,6 +3311,15 @@ struct ChanLinesGuard {
 // Checked once per call, not once per repeat: `calls[i]` is the checked call of the pair that begins at item i (fwd == NULL: none).
 static std::atomic<unsigned long long> g_many_fused_pairs{0};
 extern "C" unsigned long long dspfft_many_fused_pairs(void) { return g_many_fused_pairs.load(std::memory_order_relaxed); }
+// what the listed fused column kernel of a tile keeps in LDS behind the tile (dct_spec.h ColSpecT::RT_TABLES: decided at compile time)
+extern "C" unsigned long long dspfft_col_roundtrip_launches(void) { return g_col_roundtrip_launches.load(std::memory_order_relaxed); }
+extern "C" long long dspfft_col_roundtrip_table_bytes(int N, int K, int T)
+{
+#define DSP_RT_TAB_ENTRY(n, k, t, ...) if (N == n && K == k && T == t) { typedef dspfft::ColSpec<n, k, t, __VA_ARGS__> S; return S::RT_TABLES ? (long long)S::RT_TAB_BYTES : 0; }
+	DSPFFT_COL_SPECS(DSP_RT_TAB_ENTRY)
+#undef DSP_RT_TAB_ENTRY
+	return -1;
+}
 
 struct ManyPairs { std::vector<RtCall> calls; };
 static bool many_pair_check(const dspfft_plan *plans, const void *const *d_in, void *const *d_out, void *const *streams, int i, RtCall &c)

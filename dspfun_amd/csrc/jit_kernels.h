@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(S::T, S::WPE) jit_row_u8(const typename S::PA 
 template <class S>
 __global__ void __launch_bounds__(S::T, rt_waves_per_simd<S>()) jit_col_rt(const typename S::PA af, const typename S::PA ai, const FilterOp filt, unsigned long long *coded)
 {
-	__shared__ __attribute__((aligned(32))) unsigned char lds[S::LDS];
+	__shared__ __attribute__((aligned(32))) unsigned char lds[S::RT_LDS];      // tile + twiddle tables, where they fit (spec_fused.h)
 	col_roundtrip_body<S>(lds, af, ai, filt, coded);
 }
 

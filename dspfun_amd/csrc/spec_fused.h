@@ -40,10 +40,11 @@ struct PackedFilterOp {
 };
 
 // waves per SIMD to ask of the register allocator so that as many workgroups stay resident as the tile's LDS allows
-// (capped at 4 = 128 VGPRs): without the cap the allocator spends the whole budget and one workgroup fills a CU
+// (capped at 4 = 128 VGPRs): without the cap the allocator spends the whole budget and one workgroup fills a CU.  The tile's LDS is
+// what the fused kernel takes: the tile and, where they fit, its twiddle tables (ColSpecT::RT_LDS).
 template <class S> constexpr int rt_waves_per_simd()
 {
-	const int wgs = (int)((160 * 1024) / S::LDS), w = wgs * S::T / 256;
+	const int wgs = S::rt_resident(S::RT_LDS), w = wgs * S::T / 256;
 	return w < 1 ? 1 : w > 4 ? 4 : w;
 }
 
@@ -72,14 +73,32 @@ __device__ __forceinline__ void col_roundtrip_body(unsigned char *lds, const typ
 	long long bin, bout;
 	S::base(af, blockIdx.x, bin, bout);
 	bool hit = false;
+	// the twiddle tables behind the tile (ColSpecT::RT_TABLES): the five twiddled phases read W[m TW] and T[k] from LDS.  Their loads go
+	// out BEFORE the tile's -- loads return in order, so the tables are in LDS while the tile is still in flight -- and the barrier behind
+	// phase 0 publishes them with the tile.  Nothing writes them afterwards.  They are copied from the FORWARD plan's W and T and the inverse's
+	// stages read them too: a plan's tables are a function of N alone (engine.cpp upload_tables_t), so both plans of a pair -- same N, same
+	// kernel, or rt_col_fused does not fuse them -- hold the same bits, as mid_read has always assumed of T.
+	constexpr bool LT = S::RT_TABLES;
+	typedef typename S::template State<KIND_REDFT10> ST10;
+	typedef typename S::template State<KIND_REDFT01> ST01;
+	typename S::CX *tab = reinterpret_cast<typename S::CX *>(lds + S::LDS);
 	DSP_STAMP(0);
 	// One state object per transform, each in a scope of its own.  A thread writes and reads its slots under run-time conditions on the
 	// (opaque) thread index, so in ONE object for the whole kernel the slots a condition leaves untouched carry the previous transform's
 	// values: the forward's last butterfly (x) stayed live to the inverse's last phase and the loaded rows (pre) to mid_write -- about 100
 	// registers across every barrier on the 2160 x 8 tile (128 VGPRs, 36 of them spilled).  A fresh object starts undefined instead.
 	{
-		typename S::template State<KIND_REDFT10> st;
-		S::template prefetch<KIND_REDFT10>(af, bin, tid, st, hit);
+		ST10 st;
+		if constexpr (LT) {
+			typename S::CX tw[S::RT_TAB_ROUNDS];
+			S::rt_tab_fetch(af, tid, tw);
+			DSP_SCHED_FENCE();
+			S::template prefetch<KIND_REDFT10>(af, bin, tid, st, hit);
+			DSP_SCHED_FENCE();
+			S::rt_tab_put(tab, tid, tw);
+		} else {
+			S::template prefetch<KIND_REDFT10>(af, bin, tid, st, hit);
+		}
 		S::template phase<KIND_REDFT10, 0>(af, buf, bout, tid, st);
 		__syncthreads();
 		DSP_STAMP(1);
@@ -88,7 +107,7 @@ __device__ __forceinline__ void col_roundtrip_body(unsigned char *lds, const typ
 		// stay live across every barrier (measured: 176 VGPRs -> 1 workgroup per CU; with them: <= 128).
 		static_for<1, S::NS + 2>([&](auto ph) {
 			int t = tid; asm volatile("" : "+v"(t));
-			S::template phase<KIND_REDFT10, ph>(af, buf, bout, t, st);
+			S::template phase<KIND_REDFT10, ph, ST10, LT>(af, buf, bout, t, st, tab);
 			__syncthreads();
 			DSP_STAMP(1 + ph);
 		});
@@ -97,7 +116,7 @@ __device__ __forceinline__ void col_roundtrip_body(unsigned char *lds, const typ
 	{
 		typename S::StateMid st;
 		unsigned long long mine = 0;
-		S::mid_read(af, ai, buf, bout, t, st, filt, mine);
+		S::template mid_read<typename S::StateMid, F, LT>(af, ai, buf, bout, t, st, filt, mine, tab);
 		if (coded) {
 			unsigned int m = (unsigned int)mine;
 			for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
@@ -113,10 +132,10 @@ __device__ __forceinline__ void col_roundtrip_body(unsigned char *lds, const typ
 	}
 	typename S::PA a2 = ai;
 	asm volatile("" : "+s"(a2.W), "+s"(a2.T), "+s"(a2.out));
-	typename S::template State<KIND_REDFT01> st;
+	ST01 st;
 	static_for<1, S::NPH>([&](auto ph) {
 		asm volatile("" : "+v"(t));
-		S::template phase<KIND_REDFT01, ph>(a2, buf, bout, t, st);
+		S::template phase<KIND_REDFT01, ph, ST01, LT>(a2, buf, bout, t, st, tab);
 		if constexpr (ph + 1 < S::NPH) __syncthreads();
 		DSP_STAMP(12 + ph);
 	});

@@ -838,9 +838,9 @@ int launch_col_roundtrip(const typename S::PA &af, const typename S::PA &ai, con
 {
 	if (!is_plain(af) || !is_plain(ai)) return -5;      // (col_roundtrip_body runs the plain instantiation of both passes)
 	static DevOnce once;
-	if (int lds_rc = allow_lds_dev(once, S::LDS, col_roundtrip_kernel<S>)) return lds_rc;
+	if (int lds_rc = allow_lds_dev(once, S::RT_LDS, col_roundtrip_kernel<S>)) return lds_rc;      // tile + twiddle tables (spec_fused.h)
 	FilterOp f; f.p = filt;
-	hipLaunchKernelGGL((col_roundtrip_kernel<S>), dim3(nwork), dim3(S::T), S::LDS, (hipStream_t)stream, af, ai, f, coded);
+	hipLaunchKernelGGL((col_roundtrip_kernel<S>), dim3(nwork), dim3(S::T), S::RT_LDS, (hipStream_t)stream, af, ai, f, coded);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -849,9 +849,9 @@ int launch_col_roundtrip_packed(const typename S::PA &af, const typename S::PA &
 {
 	if (!is_plain(af) || !is_plain(ai)) return -5;
 	static DevOnce once;
-	if (int lds_rc = allow_lds_dev(once, S::LDS, col_roundtrip_packed_kernel<S>)) return lds_rc;
+	if (int lds_rc = allow_lds_dev(once, S::RT_LDS, col_roundtrip_packed_kernel<S>)) return lds_rc;
 	PackedFilterOp f; f.p = filt;
-	hipLaunchKernelGGL((col_roundtrip_packed_kernel<S>), dim3(nwork), dim3(S::T), S::LDS, (hipStream_t)stream, af, ai, f, coded);
+	hipLaunchKernelGGL((col_roundtrip_packed_kernel<S>), dim3(nwork), dim3(S::T), S::RT_LDS, (hipStream_t)stream, af, ai, f, coded);
 	HIPCHK(hipGetLastError());
 	return 0;
 }

@@ -89,6 +89,12 @@ int dspfft_execute_many_repeat(int count, const dspfft_plan *plans, const void *
  * turns the pairing off.
  * dspfft_many_fused_pairs: how many pairs this process has run that way so far (atomic, never reset). */
 unsigned long long dspfft_many_fused_pairs(void);
+/* The fused column kernel copies the twiddle factors it reads (one entry per stage twiddle, then T[k], k <= N/2; 8 bytes each) into the
+ * LDS behind its tile where that costs no resident workgroup.  For the listed kernel of N rows x K floats on T threads: the bytes it
+ * stages, 0 where it keeps loading them from global memory, -1 where no such kernel is listed.  A build-time property. */
+long long dspfft_col_roundtrip_table_bytes(int N, int K, int T);
+/* How many times this process has enqueued the fused column kernel so far, from any roundtrip entry or fused pair (atomic, never reset). */
+unsigned long long dspfft_col_roundtrip_launches(void);
 /* Streams of the library's own for the calls above: plain non-blocking HIP streams (hipStreamCreateWithFlags(hipStreamNonBlocking)),
  * for hosts without a HIP binding of their own (cgo, ctypes ...) and for hosts whose framework hands out streams from a pool:
  * two streams of torch's pool were seen sharing a hardware queue, which serialises the two frames they carry (48K instead of 56K

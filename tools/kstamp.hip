@@ -4,7 +4,7 @@
 // unstamped) -- read the phase SHARES, never compare a stamped kernel's total with an unstamped one's.
 //
 //   hipcc -std=c++17 -O3 -fno-slp-vectorize -ffp-contract=on --offload-arch=gfx950 -Idspfun_amd/csrc -Iinclude tools/kstamp.hip -o tools/kstamp
-//   tools/kstamp [pair|half|rt|zoomx|u8|trc]
+//   tools/kstamp [pair|half|rt|fused4k|zoomx|u8|trc]
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -63,12 +63,14 @@ template <class F> static void run(const char *what, int nwg, F &&launch)
 	report(what, nwg, us);
 }
 
-template <class S> static void rt_case(float *x, const char *what)
+// w: samples a row (pixels x channels).  frames = 256: config 5's luma clip (2.1 GB: nothing of it stays in the caches), copied out of x; fewer frames run in x itself
+template <class S> static void rt_case(float *x, const char *what, int w = 1920, int h = 1080, int frames = 256)
 {
-	const int w = 1920, h = 1080, frames = 256;               // config 5's luma clip (2.1 GB: nothing of it stays in the caches)
 	static float *clip = nullptr;
-	if (!clip) { CK(hipMalloc(&clip, (size_t)w * h * frames * 4)); for (int i = 0; i < frames; i += 32) CK(hipMemcpy(clip + (size_t)i * w * h, x, (size_t)w * h * 32 * 4, hipMemcpyDeviceToDevice)); }
-	x = clip;
+	if (frames == 256) {
+		if (!clip) { CK(hipMalloc(&clip, (size_t)w * h * frames * 4)); for (int i = 0; i < frames; i += 32) CK(hipMemcpy(clip + (size_t)i * w * h, x, (size_t)w * h * 32 * 4, hipMemcpyDeviceToDevice)); }
+		x = clip;
+	}
 	PassArgs af = {};
 	af.N = S::N; af.K = S::K; af.B = S::K / 2; af.ninner = w; af.ntiles = w / S::K; af.es_in = af.es_out = w; af.nb0 = frames; af.nb1 = 1;
 	af.sb0_in = af.sb0_out = (long long)w * h;
@@ -80,12 +82,12 @@ template <class S> static void rt_case(float *x, const char *what)
 	FilterOp f; f.p = mf;
 	const int nwg = af.ntiles * frames;
 	char name[128];
-	CK(hipFuncSetAttribute(reinterpret_cast<const void *>(col_roundtrip_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS));
-	snprintf(name, sizeof name, "%s, quantiser (256 frames)", what);
-	run(name, nwg, [&]() { hipLaunchKernelGGL((col_roundtrip_kernel<S>), dim3(nwg), dim3(S::T), S::LDS, 0, af, ai, f, (unsigned long long *)nullptr); });
+	CK(hipFuncSetAttribute(reinterpret_cast<const void *>(col_roundtrip_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::RT_LDS));      // tile + twiddle tables
+	snprintf(name, sizeof name, "%s, quantiser (%d frames)", what, frames);
+	run(name, nwg, [&]() { hipLaunchKernelGGL((col_roundtrip_kernel<S>), dim3(nwg), dim3(S::T), S::RT_LDS, 0, af, ai, f, (unsigned long long *)nullptr); });
 	f.p.enabled = 0;
 	snprintf(name, sizeof name, "%s, no filter", what);
-	run(name, nwg, [&]() { hipLaunchKernelGGL((col_roundtrip_kernel<S>), dim3(nwg), dim3(S::T), S::LDS, 0, af, ai, f, (unsigned long long *)nullptr); });
+	run(name, nwg, [&]() { hipLaunchKernelGGL((col_roundtrip_kernel<S>), dim3(nwg), dim3(S::T), S::RT_LDS, 0, af, ai, f, (unsigned long long *)nullptr); });
 }
 
 int main(int argc, char **argv)
@@ -142,6 +144,8 @@ int main(int argc, char **argv)
 		rt_case<ColSpec<1080, 8, 256, 12, 10, 9>>(x, "col_roundtrip 1080 K=8 T=256");
 		rt_case<ColSpec<1080, 8, 512, 12, 10, 9>>(x, "col_roundtrip 1080 K=8 T=512");
 	}
+	// the headline's fused column pair: 4K RGB frames (3840 x 3 samples a row), two of them = one launch of each stream's batch
+	if (strstr(which, "fused4k")) rt_case<ColSpec<2160, 8, 512, 12, 12, 15>>(x, "col_roundtrip 2160 K=8 T=512", 3840 * 3, 2160, 2);
 	if (strstr(which, "u8")) {
 		// motion config 5's 8-bit row ends on the luma clip: 256 x 1080 lines of 1920 samples
 		typedef RowSpec<1920, 1, 128, 8, 8, 15> S;
