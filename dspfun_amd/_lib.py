@@ -22,7 +22,7 @@ SYMBOLS = [
     "dspfft_motion_spec_blocks_u8", "dspfft_motion_spec_blocks_f32", "dspfft_motion_ispec_blocks_u8", "dspfft_motion_ispec_blocks_f32",
     "dspfft_roundtrip_topn_work_bytes", "dspfft_execute_roundtrip_topn", "dspfft_execute_roundtrip_u8_topn", "dspfft_motion_topn_blocks_work_bytes", "dspfft_motion_topn_blocks",
     "dspfft_execute_roundtrip_limit", "dspfft_execute_roundtrip_u8_limit", "dspfft_execute_roundtrip_u8_dither_limit",
-    "dspfft_execute_roundtrip_u8_packed", "dspfft_execute_roundtrip_u8_packed_rescale", "dspfft_execute_roundtrip_u8_packed_frames", "dspfft_motion_filter_packed",
+    "dspfft_execute_roundtrip_u8_packed", "dspfft_execute_roundtrip_u8_packed_rescale", "dspfft_execute_roundtrip_u8_packed_rescale_limit", "dspfft_execute_roundtrip_u8_packed_rescale_dither", "dspfft_execute_roundtrip_u8_packed_frames", "dspfft_motion_filter_packed",
     "dspfft_execute_roundtrip_u8_packed_dither", "dspfft_execute_roundtrip_u8_packed_frames_dither", "dspfft_motion_dither_u8_packed",
     "dspfft_execute_spectrogram_u8_packed", "dspfft_execute_ispectrogram_u8_packed", "dspfft_motion_spec_blocks_u8_packed", "dspfft_motion_ispec_blocks_u8_packed",
     "dspfft_plan_guru_r2r_ordered",
@@ -166,6 +166,10 @@ def bind(lib):
         lib.dspfft_execute_roundtrip_u8_packed.argtypes = [vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(MotionPacked), C.POINTER(CoeffLimit), vp, vp]
     if hasattr(lib, "dspfft_execute_roundtrip_u8_packed_rescale"):    # (as above)
         lib.dspfft_execute_roundtrip_u8_packed_rescale.argtypes = [vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(MotionPacked), vp, vp]
+    if hasattr(lib, "dspfft_execute_roundtrip_u8_packed_rescale_limit"):    # (as above)
+        lib.dspfft_execute_roundtrip_u8_packed_rescale_limit.argtypes = [vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(MotionPacked), C.POINTER(CoeffLimit), vp, vp]
+    if hasattr(lib, "dspfft_execute_roundtrip_u8_packed_rescale_dither"):
+        lib.dspfft_execute_roundtrip_u8_packed_rescale_dither.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(MotionPacked), C.POINTER(CoeffLimit), vp, vp]
     if hasattr(lib, "dspfft_execute_roundtrip_u8_packed_frames"):    # (as above)
         lib.dspfft_execute_roundtrip_u8_packed_frames.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.POINTER(MotionFilterParams), C.POINTER(MotionPacked), vp, vp]
     if hasattr(lib, "dspfft_execute_roundtrip_u8_packed_dither"):    # (as above)

@@ -32,6 +32,7 @@
 #include "block_rs_core.h"
 #include "block_packed_core.h"
 #include "block_rs_packed_core.h"
+#include "block_rs_packed_wide_core.h"
 #include "temporal_core.h"
 #include "block_spec_core.h"
 #include "block_spec_packed_core.h"
@@ -77,6 +78,9 @@ extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_topn_launch(const dspfft::BlockRsTopnArgs *a, int nwg, size_t lds, void *stream);
 // block_packed.hip's launcher behind dspfft_execute_roundtrip_u8_packed (packed 8-bit pixels through the fused block roundtrip).  Weak, as above.
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_packed_launch(const dspfft::BlockRsPackedArgs *a, int nwg, size_t lds, void *stream);
+// block_rescale_packed_limit.hip's and block_rescale_packed_dither.hip's launchers behind dspfft_execute_roundtrip_u8_packed_rescale_limit / _dither.  Weak, as above.
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_packed_limit_launch(const dspfft::BlockRsPackedWideArgs *a, int nwg, size_t lds, void *stream);
+extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_rescale_packed_dither_launch(const dspfft::BlockRsPackedWideArgs *a, int nwg, size_t lds, void *stream);
 extern "C" __attribute__((weak, visibility("hidden"))) int dspfft_block_packed_launch(const dspfft::BlockPackedArgs *a, int nwg, size_t lds, void *stream);
 // block_packed_dither.hip's launcher behind dspfft_execute_roundtrip_u8_packed_dither, and motion_dither.hip's behind dspfft_motion_dither_u8_packed
 // (dry: its checks alone).  Weak, as above.
@@ -1847,7 +1851,8 @@ struct RtArgs {
 	                                      // out8 = d_out8 (packed small blocks): the call's one kernel dithers in its tile and stores the bytes itself
 	const dspfft_motion_packed *packed;   // non-NULL: dspfft_execute_roundtrip_u8_packed's call, d_in8 / d_out8 hold packed->components bytes per pixel
 	bool packed_frames;                   // ... dspfft_execute_roundtrip_u8_packed_frames's: the interleaved full-frame pair, d_out is the float work buffer
-	bool packed_rescale;                  // ... dspfft_execute_roundtrip_u8_packed_rescale's: a rescaled block grid, out of place
+	bool packed_rescale;                  // ... dspfft_execute_roundtrip_u8_packed_rescale's: a rescaled block grid, out of place; with keep and outside_mul its _limit
+	                                      // twin's, with dither.out8 = d_out8 its _dither twin's (with or without keep)
 	bool may_slice = true;               // false: a slice of a clip (roundtrip_sliced)
 };
 // ... and what rt_check derives from them for the runners (zero before)
@@ -1867,7 +1872,8 @@ struct RtCall : RtArgs {
 	bool temporal;                        // blocks along time that the plans' own passes cannot run (rt_temporal): temporal_rt.hip's kernel runs the call
 	TemporalArgs tp;                      // its arguments but the tables (rt_run_temporal)
 	BlockPackedDitherArgs pk;             // packed pixels (rt_packed): block_packed.hip's kernel runs the call, or (c.dither) block_packed_dither.hip's
-	BlockRsPackedArgs pg;                 // packed pixels over a rescaled block grid (rt_packed_grid): block_rescale_packed.hip's kernel runs the call
+	BlockRsPackedWideArgs pg;             // packed pixels over a rescaled block grid (rt_packed_grid): block_rescale_packed.hip's kernel runs the call, or, with a
+	                                      // coefficient limit (pg.keep) or -d (pg.dither), one of the wide tile's (block_rs_packed_wide_core.h)
 	MotionFilterPacked mfp;               // packed pixels over full frames (rt_packed_frames): the filter of the fused column kernel's twin,
 	dspfft_motion_filter_params pf_fp;    // ... and of the stand-alone kernel (the call's, with the frame's geometry), over
 	int pf_h, pf_w; long long pf_frames;  // ... that many frames of h x w pixels
@@ -2210,6 +2216,8 @@ int rt_run_packed(const RtCall &c)
 // and offset times `components`, block_rescale_packed.hip's kernel.  The entry has refused null plans, buffers and c.packed and f64 plans.
 // 0: c.pg is set; < 0: the call cannot run.  Nothing is launched here.
 constexpr const char *kPackedGrid = "roundtrip on packed 8-bit pixels over a rescaled grid of blocks";
+constexpr const char *kPackedGridLimit = "roundtrip on packed 8-bit pixels over a rescaled grid of blocks with a coefficient limit";
+constexpr const char *kPackedGridDither = "dithered roundtrip on packed 8-bit pixels over a rescaled grid of blocks";
 // the pixels from a clip's first to one past its last, as the plan's block geometry lays it out (out: the output side)
 long long block_clip_span(const BlockGeom &g, bool out)
 {
@@ -2220,7 +2228,8 @@ long long block_clip_span(const BlockGeom &g, bool out)
 int rt_packed_grid(RtCall &c)
 {
 	const dspfft_plan fwd = c.fwd, inv = c.inv;
-	const char *const what = kPackedGrid;
+	const bool dither = c.dither.out8 != nullptr;           // motion -d: the store's three phases in the wide tile (block_rs_packed_wide_core.h)
+	const char *const what = dither ? kPackedGridDither : c.outside_mul > 0 ? kPackedGridLimit : kPackedGrid;          // (outside_mul: the _limit entry's call, whatever its keep)
 	if (int rc = rt_filter(c, what)) return rc;
 	const int C = c.packed->components;
 	if (C < 2 || C > PACKED_MAX_COMPS) return fail(-2, "%s: components must be 2, 3 or 4 bytes per pixel, got %d (one component is the planar call)", what, C);
@@ -2236,33 +2245,74 @@ int rt_packed_grid(RtCall &c)
 	if (in0 < out0 + out_bytes && out0 < in0 + in_bytes)
 		return fail(-2, "%s: the input clip (%llu bytes) and the output clip (%llu bytes) overlap; the call is out of place (the clips have different extents)", what, in_bytes, out_bytes);
 	rt_trc_ends(c);
-	BlockRsPackedArgs &a = c.pg;
+	BlockRsPackedWideArgs &a = c.pg;
 	memset((void *)&a, 0, sizeof a);
 	rt_block_args(c, a);
 	rt_tables(c, a);
 	a.ox = i.nx; a.oy = i.ny; a.oz = i.nz;
+	// --coeff-limit: at or above the embedding's count nothing is dropped (motion.c:654-657) and the call is the one without a limit
+	const int ex = std::max(f.nx, i.nx);
+	const bool limit = c.keep && c.keep < (size_t)ex * std::max(f.ny, i.ny) * std::max(f.nz, i.nz);
+	const bool wide = limit || dither;
 	// the plans count pixels; the kernel addresses bytes
 	a.sy_in *= C; a.sz_in *= C; a.sxb_in *= C; a.sy_out *= C; a.sz_out *= C; a.sxb_out *= C;
 	long long nwg = 1;
 	for (int d = 0; d < a.nd; d++) { a.bis[d] *= C; a.bos[d] *= C; nwg *= a.bn[d]; }
 	// the tile of a component block: the embedding's rows and planes, the active columns (block_rs_packed_core.h)
-	const int mx = std::min(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
+	// with a limit or -d: the wide tile's columns, the embedding's or `scaled`'s, and rs_packed_group_of's rule on that tile
+	const int mx = wide ? rs_packed_wide_tw(f.nx, i.nx, limit) : std::min(f.nx, i.nx), my = std::max(f.ny, i.ny), mz = std::max(f.nz, i.nz);
 	int G = rs_packed_group_of(mx, my, mz, f.ny * f.nz, i.ny * i.nz, C, a.nxb);
-	if (const char *e = getenv("DSPFFT_PACKED_G")) { if (atoi(e) > 0) G = std::min(atoi(e), a.nxb); }      // experiments (tools/bench_motion_packed_rescale.py)
+	bool forced = false;
+	if (const char *e = getenv("DSPFFT_PACKED_G")) { if (atoi(e) > 0) { G = std::min(atoi(e), a.nxb); forced = true; } }      // experiments (tools/bench_motion_packed_rescale.py)
 	const size_t block_bytes = (size_t)mz * my * C * mx * sizeof(float);
 	G = rt_lds_group(G, block_bytes);
-	if (!G) return fail(-2, "%s: the %d component tiles of a %dx%dx%d embedding (%zu bytes) and the tables do not fit a workgroup's 64 KB of LDS", what, C, std::max(f.nx, i.nx), my, mz, block_bytes);
+	// -d: the error table and, with one lane per plane, the dither lanes' error rows lie behind the tile, the tables and the counter.  The walk leaves
+	// most lanes idle, so the rule's group gives way until four workgroups share a CU's 160 KB of LDS (40 KB each) and one's walk hides behind the
+	// others' passes: the fastest group of the -d sweeps with a limit and of 8x8x8 -> 4x4x4 without, within 12 % of the fastest elsewhere
+	// (profiles/r23_motion_packed_rescale_limit_dither.txt)
+	// Which walk (rs_packed_dither_by_rows) is decided on the planes of the largest tile that fits; with oy lanes per plane the group then gives way
+	// until its planes fill their rounds of lanes (1x8x8 -> 1x16x16 rgb24: 10.5 ms at ten pixel blocks, 480 lanes in two rounds; 13.8 at twelve, three)
+	const bool by_rows = dither && rs_packed_dither_by_rows(i.ny, i.nx, i.nz * C * std::max(1, G));
+	const auto dither_lds = [&](int g) { return (size_t)g * block_bytes + sizeof(TrcU8Tab) + 16 + rs_packed_wide_dither_bytes(i.nx, i.nz, C, g, true, by_rows); };
+	const auto rounds = [&](int g) { return (i.nz * C * g * i.ny + BLOCK_THREADS - 1) / BLOCK_THREADS; };
+	while (dither && G > 0 && dither_lds(G) > 64 * 1024) G--;
+	while (dither && !forced && G > 1 && dither_lds(G) > 40 * 1024) G--;
+	while (by_rows && !forced && G > 1 && rounds(G) == rounds(G + 1)) G--;
+	if (!G && dither)
+		return fail(-2, "%s: the %d component tiles of a %dx%dx%d embedding, %d columns each (%zu bytes), the tables and the dither's error rows do not fit a workgroup's 64 KB of LDS", what, C, ex, my, mz, mx, block_bytes);
+	if (!G) return fail(-2, "%s: the %d component tiles of a %dx%dx%d embedding (%zu bytes) and the tables do not fit a workgroup's 64 KB of LDS", what, C, ex, my, mz, block_bytes);
+	if (limit) {
+		// what the reference ranks outside min(block, scaled): the coefficient without the forward plan's scales, times outside_mul (block_rs_core.h)
+		bool listed = false;
+#define DSP_RS_SEL(K_, MX_) listed = listed || (mx == MX_ && rs_topn_keys(mx * my * mz) == K_);
+		DSPFFT_RS_TOPN_SHAPES(DSP_RS_SEL)
+#undef DSP_RS_SEL
+		if (!listed) return fail(-2, "%s: no selection for a %dx%dx%d embedding", what, mx, my, mz);
+		a.keep = (unsigned int)c.keep; a.key_mul = (float)(c.outside_mul / (double)a.f.scale);
+		for (int k = 0; k < 3; k++) a.key_mul0[k] = 1.f / a.f.out0[k];
+	}
+	if (dither) { a.dither = 1; a.sf = c.dither.sf; a.norm = c.dither.norm; a.slots = packed_dither_slots(i.nz, C, G); a.by_rows = by_rows; }
 	a.tw = mx; a.G = G; a.pitch = G * C * mx; a.ngroups = (a.nxb + G - 1) / G; a.gdiv = make_div((uint32_t)a.ngroups);
 	nwg *= a.ngroups;
 	if (nwg > 0x7fffffffLL) return fail(-2, "%s: too many blocks for one launch (more than 2^31 - 1 workgroups)", what);
 	a.comps = C;
 	if (c.fp) for (int k = 0; k < C; k++) { a.damp[k] = c.packed->damp[k]; a.boost[k] = c.packed->boost[k]; a.grey_add[k] = c.packed->grey_add[k]; }
+	if (dither && !dspfft_block_rescale_packed_dither_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale_packed_dither.hip)", what);
+	if (limit && !dither && !dspfft_block_rescale_packed_limit_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale_packed_limit.hip)", what);
 	if (!dspfft_block_rescale_packed_launch) return fail(-3, "%s: not built into this library (the kernel is HIP-only, block_rescale_packed.hip)", what);
 	c.nwg = (int)nwg; c.lds = (size_t)G * block_bytes;
 	return 0;
 }
 int rt_run_packed_grid(const RtCall &c)
 {
+	if (c.pg.dither) {
+		if (int rc = dspfft_block_rescale_packed_dither_launch(&c.pg, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (%s): backend code %d", kPackedGridDither, rc);
+		return 0;
+	}
+	if (c.pg.keep) {
+		if (int rc = dspfft_block_rescale_packed_limit_launch(&c.pg, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (%s): backend code %d", kPackedGridLimit, rc);
+		return 0;
+	}
 	if (int rc = dspfft_block_rescale_packed_launch(&c.pg, c.nwg, c.lds, c.stream)) return fail(-4, "kernel launch failed (%s): backend code %d", kPackedGrid, rc);
 	return 0;
 }
@@ -3250,6 +3300,47 @@ extern "C" int dspfft_execute_roundtrip_u8_packed_rescale(dspfft_plan fwd, dspff
 	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", kPackedGrid);
 	RtCall c = {};
 	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.packed_rescale = true;
+	c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
+}
+
+// ... with motion --coeff-limit (block_rescale_packed_limit.hip): cl->d_work and cl->work_bytes are not read
+extern "C" int dspfft_execute_roundtrip_u8_packed_rescale_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
+                                                                const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed, const dspfft_coeff_limit *cl,
+                                                                unsigned long long *d_coeffs_coded, void *stream)
+{
+	const char *const what = kPackedGridLimit;
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", what);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", what);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", what);
+	if (!cl) return fail(-1, "%s: null dspfft_coeff_limit (dspfft_execute_roundtrip_u8_packed_rescale takes none)", what);
+	if (!cl->keep) return fail(-1, "%s: keep must be at least 1 (dspfft_execute_roundtrip_u8_packed_rescale takes no limit)", what);
+	if (!std::isfinite(cl->outside_mul) || !(cl->outside_mul > 0)) return fail(-1, "%s: outside_mul must be finite and > 0 (1 for motion's 3-D blocks)", what);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.mul8 = out_mul; c.fp = fp; c.packed = packed; c.packed_rescale = true;
+	c.keep = cl->keep; c.outside_mul = cl->outside_mul;
+	c.coded = d_coeffs_coded; c.stream = stream;
+	return roundtrip_core(c);
+}
+
+// ... with motion's -d (block_rescale_packed_dither.hip: the kernel dithers in its tile and stores the bytes itself, so the call carries both d_out8
+// and c.dither); cl NULL: no coefficient limit
+extern "C" int dspfft_execute_roundtrip_u8_packed_rescale_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double scalefactor,
+                                                                 double normalization, const dspfft_motion_filter_params *fp, const dspfft_motion_packed *packed,
+                                                                 const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *stream)
+{
+	const char *const what = kPackedGridDither;
+	if (!fwd || !inv || !d_in || !d_out) return fail(-1, "%s: null plan or buffer", what);
+	if (!packed) return fail(-1, "%s: null dspfft_motion_packed", what);
+	if (fwd->f64 || inv->f64) return fail(-1, "%s takes f32 plans", what);
+	if (cl && !cl->keep) return fail(-1, "%s: coefficient limit: keep must be at least 1 (pass NULL for no limit)", what);
+	if (cl && (!std::isfinite(cl->outside_mul) || !(cl->outside_mul > 0))) return fail(-1, "%s: coefficient limit: outside_mul must be finite and > 0 (1 for motion's 3-D blocks)", what);
+	if (!(scalefactor > 0) || !(normalization > 0) || !std::isfinite(scalefactor) || !std::isfinite(normalization))
+		return fail(-1, "%s: scalefactor and normalization must be finite and > 0", what);
+	RtCall c = {};
+	c.fwd = fwd; c.inv = inv; c.d_in8 = d_in; c.d_out8 = d_out; c.dither = Dither{d_out, scalefactor, normalization}; c.mul8 = scalefactor * normalization * normalization;
+	c.fp = fp; c.packed = packed; c.packed_rescale = true;
+	if (cl) { c.keep = cl->keep; c.outside_mul = cl->outside_mul; }
 	c.coded = d_coeffs_coded; c.stream = stream;
 	return roundtrip_core(c);
 }

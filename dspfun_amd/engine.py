@@ -263,16 +263,34 @@ class Plan:
         self._check(self._lib.dspfft_execute_roundtrip_u8_packed(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
                                                                  *self._tail(filter, d_coded, stream, *between)))
 
-    def roundtrip_u8_packed_rescale(self, inv, d_in_u8, d_out_u8, out_mul, packed, filter=None, d_coded=0, stream=0):
+    def roundtrip_u8_packed_rescale(self, inv, d_in_u8, d_out_u8, out_mul, packed, filter=None, d_coded=0, stream=0, coeff_limit=0, outside_mul=1.0):
         """dspfft_execute_roundtrip_u8_packed_rescale: motion -b with -s over a block grid on packed 8-bit pixels (rgb24, rgba ...), one launch.
         self / inv: the planar grid pair motion_grid_plans(shape, block, scaled) with scaled != block, planned over the clips in pixels; d_in_u8
         holds info["in_shape"] and d_out_u8 info["out_shape"] pixels of packed.components bytes, and the two must not overlap.  out_mul:
         info["out_mul"].  packed: motion_packed(..., normalization=info["normalization"], scalefactor=info["scalefactor"]) -- its damp, boost
         and grey_add (by byte position) replace the filter's; filter: the planar grid call's (active = info["active"], minbuf_hw and block_depth
-        of the embedding), or None.  Needs no work buffer and takes no coefficient limit."""
+        of the embedding), or None.  Needs no work buffer.  coeff_limit: motion --coeff-limit per component block over the whole embedding
+        (dspfft_execute_roundtrip_u8_packed_rescale_limit; 0: none) with outside_mul = info["limit_outside_mul"]; the bytes are
+        roundtrip_u8_limit's on each component's plane."""
         pk = C.byref(packed) if packed is not None else None
+        if coeff_limit:
+            cl = self._coeff_limit(inv, coeff_limit, outside_mul, work=False)[0]
+            self._check(self._lib.dspfft_execute_roundtrip_u8_packed_rescale_limit(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
+                                                                                   *self._tail(filter, d_coded, stream, pk, C.byref(cl))))
+            return
         self._check(self._lib.dspfft_execute_roundtrip_u8_packed_rescale(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(out_mul),
                                                                          *self._tail(filter, d_coded, stream, pk)))
+
+    def roundtrip_u8_packed_rescale_dither(self, inv, d_in_u8, d_out_u8, scalefactor, normalization, packed, filter=None, coeff_limit=0, outside_mul=1.0,
+                                           d_coded=0, stream=0):
+        """dspfft_execute_roundtrip_u8_packed_rescale_dither: roundtrip_u8_packed_rescale with motion's -d, one launch -- the Floyd-Steinberg store
+        runs in the kernel's LDS tile, over the planes of `scaled`.  Arguments as roundtrip_u8_packed_rescale's, with info["scalefactor"] and
+        info["normalization"] in place of out_mul.  The bytes are roundtrip_u8_dither's (with coeff_limit and outside_mul: its limit twin's) on
+        each component's plane.  Needs no work buffer; out of place."""
+        cl = self._coeff_limit(inv, coeff_limit, outside_mul, work=False)[0] if coeff_limit else None
+        between = (C.byref(packed) if packed is not None else None, C.byref(cl) if cl is not None else None)
+        self._check(self._lib.dspfft_execute_roundtrip_u8_packed_rescale_dither(self._h, inv._h, C.c_void_p(d_in_u8), C.c_void_p(d_out_u8), float(scalefactor),
+                                                                                float(normalization), *self._tail(filter, d_coded, stream, *between)))
 
     def roundtrip_u8_packed_frames(self, inv, d_in_u8, d_out_u8, d_work, out_mul, packed, filter=None, d_coded=0, stream=0):
         """dspfft_execute_roundtrip_u8_packed_frames: motion's default block 0x0x1 on packed 8-bit pixels (rgb24, rgba ...) -- every component of

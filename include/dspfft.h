@@ -466,11 +466,49 @@ int dspfft_execute_roundtrip_u8_packed(dspfft_plan fwd, dspfft_plan inv, const u
  *       2^31 - 1 workgroups
  *   -3  a library built without the HIP kernel
  *   -4  a launch failure
- * Not implemented on a packed rescaled grid, each refused where a call could ask for it: --coeff-limit (this entry takes no limit), -d,
- * --spectrogram / --ispectrogram, -s over full frames or one block, float and padded (rgb0) formats. */
+ * --coeff-limit and -d are the two entries below (this one takes no limit).  Not implemented on a packed rescaled grid, each refused where a
+ * call could ask for it: --spectrogram / --ispectrogram, -s over full frames or one block, float and padded (rgb0) formats. */
 int dspfft_execute_roundtrip_u8_packed_rescale(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
                                                const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
                                                unsigned long long *d_coeffs_coded, void *hip_stream);
+
+/* dspfft_execute_roundtrip_u8_packed_rescale with motion --coeff-limit (motion -b 8x8x8 -s 4x4x4 --coeff-limit 16 -c pixel_format=rgb24): the same
+ * pair, buffers, `packed` and filter, out of place (overlapping clips are refused), stream-ordered, no allocation, NO work buffer: cl->d_work and
+ * cl->work_bytes are not read.  Every component block keeps its cl->keep coefficients of largest magnitude ahead of the filter; the reference
+ * ranks the whole embedding M = max(block, scaled) (motion.c:652-668), so cl->outside_mul follows dspfft_coeff_limit's rule exactly as in
+ * dspfft_execute_roundtrip_u8_limit on a rescaled grid.  ONE kernel (block_rescale_packed_limit.hip) on a WIDER tile than the plain call's: MX
+ * columns per component block instead of min(block, scaled), because the selection reads the whole embedding; the forward passes run unpruned
+ * (block_rescale_topn.hip's phases between the packed ends), the selection is topn_core.h's per component block, and with preserve_dc = dc the
+ * restored DC is the one from before the selection, per component.
+ * The bytes EQUAL those of dspfft_execute_roundtrip_u8_limit on the same planar grid pair on each component's plane with that component's damp,
+ * boost and grey_add, and d_coeffs_coded the sum of the planar counts.  keep >= MX MY MZ is the plain call, with the same bytes.
+ * Nothing is launched when it fails: dspfft_execute_roundtrip_u8_packed_rescale's codes and reasons under this entry's name, and
+ *   -1  cl NULL, keep == 0, outside_mul not finite or not > 0
+ *   -2  a pair whose `components` tiles of the WHOLE embedding plus the tables do not fit 64 KB of LDS: a 16 x 16 x 16 embedding at four components
+ *       (three fit, one pixel block per workgroup); an embedding without a selection (none among the extents the grid takes)
+ *   -3  a library built without the HIP kernel */
+int dspfft_execute_roundtrip_u8_packed_rescale_limit(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double out_mul,
+                                                     const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                                     const dspfft_coeff_limit *cl, unsigned long long *d_coeffs_coded, void *hip_stream);
+
+/* dspfft_execute_roundtrip_u8_packed_rescale with motion's -d, with or without --coeff-limit (cl as in the _limit entry above; NULL: no limit):
+ * the same pair, buffers, `packed` and filter, out of place, stream-ordered, no allocation, NO work buffer.  scalefactor and normalization replace
+ * out_mul (= scalefactor normalization^2) as in dspfft_execute_roundtrip_u8_dither.  ONE kernel (block_rescale_packed_dither.hip): the inverse's x
+ * pass writes its SX floats back to the tile -- a component block is SX columns wide, MX with a limit --, the oz planes of oy x SX floats of every
+ * tile block are the planes of the Floyd-Steinberg store, oy lanes walk one plane -- row y two pixels behind row y - 1, the errors handed down by
+ * shuffles, each pixel with dither_core.h's arithmetic in the reference's order --, and the bytes leave through the packed store.  The error table
+ * (2 KB) lies behind the tile, the transfer tables and the counter.
+ * dspfft_plan_set_u8_trc on either plan is honoured as in dspfft_execute_roundtrip_u8_packed_dither.
+ * The bytes EQUAL those of dspfft_execute_roundtrip_u8_dither (with cl: dspfft_execute_roundtrip_u8_dither_limit) on the same planar grid pair on
+ * each component's plane with that component's damp, boost and grey_add, and d_coeffs_coded the sum of the planar counts.
+ * Nothing is launched when it fails: the codes and reasons of the two entries above under this entry's name, and
+ *   -1  scalefactor or normalization not finite or not > 0; cl non-NULL with keep == 0 or a bad outside_mul
+ *   -2  a pair whose tile, tables and error table do not fit 64 KB of LDS even with one pixel block per workgroup
+ *   -3  a library built without the HIP kernel */
+int dspfft_execute_roundtrip_u8_packed_rescale_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double scalefactor, double normalization,
+                                                      const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
+                                                      const dspfft_coeff_limit *cl /* NULL: no --coeff-limit */,
+                                                      unsigned long long *d_coeffs_coded, void *hip_stream);
 
 /* The small-block call on FULL FRAMES of packed pixels -- the reference's default block -b 0x0x1, what `motion -q 20 in.png out.png` or
  * `motion -c pixel_format=rgb24` on a clip runs: every component of every frame is one block (:613-615).  An entry of its own because the
@@ -522,10 +560,10 @@ int dspfft_execute_roundtrip_u8_packed_frames(dspfft_plan fwd, dspfft_plan inv, 
  * Nothing is launched when it fails: dspfft_execute_roundtrip_u8_packed's codes and reasons under this entry's name, and
  *   -1  scalefactor or normalization not finite or not > 0
  *   -2  a tile whose component blocks, tables, error table (2 KB) and error rows (NX doubles per dither lane) do not fit 64 KB of LDS;
- *       different extents in fwd and inv: -d on a packed rescaled grid is not implemented (its tile keeps only min(block, scaled) columns and
- *       has no room for the scaled planes)
+ *       different extents in fwd and inv: -d on a packed rescaled grid is not implemented by this entry (its tile has one block's extents); that
+ *       call is dspfft_execute_roundtrip_u8_packed_rescale_dither's
  *   -3  a library built without the HIP kernel
- * Not implemented with -d on packed pixels: a rescaled grid, one 3-D block, float and padded (rgb0) formats. */
+ * Not implemented with -d on packed pixels: one 3-D block, float and padded (rgb0) formats. */
 int dspfft_execute_roundtrip_u8_packed_dither(dspfft_plan fwd, dspfft_plan inv, const uint8_t *d_in, uint8_t *d_out, double scalefactor, double normalization,
                                               const dspfft_motion_filter_params *filter, const dspfft_motion_packed *packed,
                                               const dspfft_coeff_limit *cl /* NULL: no --coeff-limit */,
